@@ -14,8 +14,11 @@ process per GPU (RCCL over xGMI).  The default is the headline, BASELINE.json co
     cfg4  ViT-MHLA-Base 384x384 patch16, 577 tokens, 64 img/GPU, --dtype bf16 | fp8
 
 A step = zero_grad -> forward -> cross-entropy -> backward -> gradient all-reduce -> AdamW on one synthetic
-batch already resident in HBM.  Rank 0 prints ONE JSON line.  Per-launch GEMM timing (HIP events on the launch
-stream) runs in extra, un-timed steps AFTER the timed region.
+batch already resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and
+prints the headline figures.  --full adds what takes runs of its own: per-launch GEMM timing (HIP events on the launch
+stream, in extra, un-timed steps AFTER the timed region) with the roofline figures derived from it, and the CPU
+baseline.  --dump-outputs DIR writes what the timed step computes from the seeded weights and batch (loss, parameters,
+gradients) as DIR/<name>.npy: after the timed region the run state is put back and the step runs once more, un-timed.
 """
 import argparse
 import glob
@@ -38,6 +41,7 @@ BF16_DENSE_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MF
 F32_MFMA_PEAK_TFLOPS = 157.3
 FP8_DENSE_PEAK_TFLOPS = 5000.0
 PROFILE_DIR = os.path.join(ROOT, "profiles")
+DUMP_MAX_ELEMS = 4 << 20            # per dumped array: 16 MiB of float32, well inside the 64 MB a dump may take
 
 
 def traffic_profile(cfg, dtype):
@@ -197,6 +201,42 @@ def csrc_sha16():
     return h.hexdigest()[:16]
 
 
+def restore_seeded_state(pkg, model, opt, weights):
+    """Put the run back where it began: the seeded weights (`weights`: clones in model.parameters() order), zero AdamW
+    moments and step count.  Why the dump needs it: a few leaf gradients (latent_proj fold, cls_token, pos_embed,
+    patch embedding) are summed with fp32 atomics whose order varies, AdamW's normalised update turns those last-bit
+    differences into +-lr steps, and after a handful of steps two runs of one build differ in every parameter (measured
+    at the headline configuration: gradients 4e-8 rel-L2 apart after one step, 5e-3 after two, 0.14 after 25) -- no
+    basis for comparing two builds.  One step from the seeded state is reproducible to rounding.  (The fp8 mode's
+    per-site scale history is not part of this state and stays as the run left it.)"""
+    with torch.no_grad():
+        for p, w in zip(model.parameters(), weights):
+            p.copy_(w)
+        for g in opt.groups:
+            g["m"].zero_()
+            g["v"].zero_()
+    opt.steps = 0
+    pkg.functional.invalidate_weight_cache()       # the bf16 mirrors are re-cast from the restored weights at next use
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of the timed step holds after a call, as float32 <name>.npy files: the loss it returned, the
+    parameters it updated and the gradients it left in .grad (model.parameters() order, flattened and
+    concatenated).  Arrays above DUMP_MAX_ELEMS elements are cut to a fixed, seeded sample of positions (sorted, so
+    that two builds are compared element for element)."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": torch.cat([p.detach().reshape(-1) for p in params]),
+              "grads": torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])}
+    for name, t in arrays.items():
+        t = t.to(torch.float32)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(1234).randint(0, t.numel(), size=DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 def cpu_baseline(cfg, model, segs_np):
     """The CPU oracle (oracle/favit_oracle.py, a port of the reference's PyTorch-CPU path) timed on this box's
     host cores: same model configuration and weights, fp32, 1 warm-up + N timed fwd+bwd steps (bounded sample)."""
@@ -274,10 +314,17 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default: the configuration's own)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
                     help="bf16 = the headline; fp8 = the BASELINE.json configs[3] GEMM path (cfg4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-launch GEMM timing steps (roofline, "
+                         "gemm_families, step_hbm) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more, un-timed, from the seeded weights and a fresh "
+                         "optimizer state, and write its loss, parameters and gradients as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of the larger arrays): the same from run to run up to rounding")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--backend", default=os.environ.get("FAVIT_DIST_BACKEND", "nccl"),
                     help="torch.distributed backend (nccl = RCCL; gloo only for rehearsing ranks on one GPU)")
-    ap.add_argument("--no-gemm-trace", action="store_true")
+    ap.add_argument("--no-gemm-trace", action="store_true", help="--full without the per-launch GEMM timing steps")
     ap.add_argument("--slic-noise", action="store_true", help="--slic on the step's N(0,1) noise images (worst case)")
     ap.add_argument("--graph", action="store_true", help="cfg2 / cfg4: replay the step from HIP graphs as well")
     ap.add_argument("--no-graph", action="store_true", help="cfg1 / cfg3: eager launches instead of the replayed HIP graph")
@@ -383,6 +430,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    seeded = [p.detach().clone() for p in model.parameters()] if args.dump_outputs else None
     log(f"rank {rank}/{world}: {args.config} model built, warming up")
     for _ in range(args.warmup):
         step()
@@ -421,6 +469,12 @@ def main():
             json.dump(rep, fh, indent=1)
         log(f"NON-FINITE values in the step: {json.dumps(rep)}  (written to {path})")
         sys.exit(3)
+    if args.dump_outputs:                            # every rank: the step's all-reduce is collective
+        restore_seeded_state(pkg, model, opt, seeded)
+        dump_loss = step()
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dump_loss, model)
 
     # PCIe-inclusive rate (informational): every step consumes a fresh uint8 batch from pinned host memory
     pcie = None
@@ -511,7 +565,7 @@ def main():
     # per-launch GEMM timing: two extra EAGER steps after the timed region (events cannot be captured in a graph).
     # Every rank runs them (the all-reduce inside opt.step() is collective); only rank 0 records events.
     trace, traced_steps, opt_ms = None, 0, None
-    if not args.no_gemm_trace:
+    if args.full and not args.no_gemm_trace:
         trace = [] if rank == 0 else None
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         for s in range(2):
@@ -606,7 +660,7 @@ def main():
                                    "floor_ms_at_peak": round(hb / (HBM_PEAK_GBPS * 1e9) * 1e3, 3),
                                    "source": os.path.relpath(tsrc, ROOT), "stale": bool(stale),
                                    "what": "sum over every kernel of the step of (2*FETCH_SIZE + WRITE_SIZE) x launches"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config, model, segs_np)
         print(json.dumps(out), flush=True)
     if world > 1:

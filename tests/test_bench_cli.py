@@ -1,10 +1,12 @@
 """bench.py is the measurement contract (one JSON line per run): run it for real, small, on the GPU box -- every
-configuration, the dropout row, the fp8 mode and the CPU-baseline leg -- and check the line's shape."""
+configuration, the dropout row, the fp8 mode and the CPU-baseline leg (all with --full: the roofline and the CPU
+baseline live behind it), the plain run and its --dump-outputs files -- and check the line's shape."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,7 +47,7 @@ def _check(j, steps, warmup, dtype="bf16"):
                                        ("cfg5", ["--batch", "16"]), ("cfg2", ["--batch", "16", "--dtype", "fp32"]),
                                        ("cfg4", ["--batch", "2", "--dtype", "fp8"])])
 def test_bench_line(cfg, extra):
-    j = _run("--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra)
+    j = _run("--config", cfg, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", *extra)
     _check(j, 3, 1, dtype="fp8" if "fp8" in extra else "fp32" if "fp32" in extra else "bf16")
     assert j["config"]["baseline_config"] == cfg
     if "--slic" in extra:
@@ -83,12 +85,57 @@ def test_bench_refuses_to_report_a_non_finite_run(tmp_path):
 
 def test_bench_cpu_baseline_leg():
     """The oracle-timed CPU baseline (kind "port") on the small configuration."""
-    j = _run("--config", "cfg1", "--steps", "2", "--warmup", "1")
+    j = _run("--config", "cfg1", "--steps", "2", "--warmup", "1", "--full")
     _check(j, 2, 1)
     c = j["cpu_baseline"]
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line keeps the headline keys and carries nothing that takes runs of its own (GEMM-trace
+    steps, CPU baseline).  --dump-outputs writes loss, parameters and gradients of ONE step of the timed path from the
+    seeded weights on the seeded batch (bench.py puts the run state back after the timed steps) as float32 .npy, at
+    most 64 MB in all, and the same arguments give the same inputs: two runs must agree as far as the kernels are
+    reproducible (run-to-run reproducibility), and both must agree with a run whose only step
+    really is the first one (--steps 1 --warmup 0).  The bounds, from that and the number formats:
+      * loss: the forward has no atomics, so only a few fp32 ulps are allowed (1e-6 relative);
+      * gradients: some leaf gradients are summed with fp32 atomics in varying order, <= ~3,200 addends (16 x 197 token
+        rows): ~sqrt(n) * 2^-24 = 3e-6 relative per sum, nothing downstream of them in the backward -> 1e-4 rel-L2;
+      * parameters: one AdamW step moves an element by at most ~lr = 1e-4 (the first update is lr * g / |g|, and the
+        sign of a mathematically zero gradient is noise), so two runs differ by <= 2e-4 per element against weights of
+        rms ~0.02: 1e-2 rel-L2 holds whatever the signs do, and any other seed or batch is far outside all three."""
+    lines, dumps = [], []
+    for run, steps, warmup in (("a", 3, 1), ("b", 3, 1), ("first", 1, 0)):
+        d = tmp_path / run
+        j = _run("--gpus", "1", "--config", "cfg2", "--batch", "16", "--steps", str(steps), "--warmup", str(warmup),
+                 "--dump-outputs", str(d))
+        assert j["steps"] == steps and j["warmup"] == warmup
+        lines.append(j)
+        assert sorted(os.listdir(str(d))) == ["grads.npy", "loss.npy", "params.npy"]
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= 64e6
+        dumps.append({n: np.load(str(d / f"{n}.npy")) for n in ("loss", "params", "grads")})
+    for j, out in zip(lines, dumps):
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert k in j, k
+        assert j["ms_per_step"] > 0 and j["value"] > 0
+        assert abs(j["value"] - 16 * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"]
+        for k in ("roofline", "gemm_families", "gemm_share_of_step", "step_hbm", "optimizer_and_allreduce_wait_ms",
+                  "cpu_baseline"):
+            assert k not in j, k
+        for a in out.values():
+            assert a.dtype == np.float32 and a.ndim == 1 and np.isfinite(a).all()
+        assert out["loss"].shape == (1,)
+        assert out["params"].shape == out["grads"].shape and out["params"].size > 1 << 20 and np.abs(out["grads"]).max() > 0
+    # the dumped loss is the loss of the first step from the seeded state: the line of the one-step run reports it
+    first = lines[2]["loss"]
+    for out in dumps:
+        assert abs(float(out["loss"][0]) - first) <= 1e-5 * max(1.0, abs(first))
+    rel = lambda x, y: float(np.linalg.norm(x.astype(np.float64) - y) / np.linalg.norm(y.astype(np.float64)))
+    for x, y in ((dumps[0], dumps[1]), (dumps[0], dumps[2])):
+        print({n: rel(x[n], y[n]) for n in x})
+        assert rel(x["loss"], y["loss"]) < 1e-6 and rel(x["grads"], y["grads"]) < 1e-4 and rel(x["params"], y["params"]) < 1e-2
 
 
 def test_bench_two_ranks_gloo_on_one_gpu():
@@ -100,7 +147,7 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     port = 36000 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--batch", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--batch", "16", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

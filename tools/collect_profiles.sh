@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 run_stats() {   # name, bench args...
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$name -- python3 $root/bench.py "$@" \
-    --steps 12 --warmup 3 --no-cpu-baseline > $out/bench_$name.json 2> $out/bench_$name.err || echo "stats $name failed"
+    --steps 12 --warmup 3 --full --no-cpu-baseline > $out/bench_$name.json 2> $out/bench_$name.err || echo "stats $name failed"
   find $out/stats_$name -name "*kernel_trace.csv" -delete
   local st=$(find $out/stats_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$st" ] && cp $st $prof/${tag}_bench_kernel_stats_$name.csv
@@ -56,15 +56,16 @@ run_pmc cfg3 cfg3 bf16 --config cfg3
 run_stats cfg5 --config cfg5
 run_pmc cfg5 cfg5 bf16 --config cfg5
 fi
-# un-profiled bench lines of every configuration on this box (the default command first, with its CPU baseline)
+# un-profiled bench lines of every configuration on this box, with --full for the roofline keys (the default command
+# first, with its CPU baseline)
 run_plain() {   # name, bench args...
   local name=$1; shift
-  python3 $root/bench.py "$@" > $out/plain_$name.json 2> $out/plain_$name.err || echo "plain $name failed"
+  python3 $root/bench.py --full "$@" > $out/plain_$name.json 2> $out/plain_$name.err || echo "plain $name failed"
   grep '^{' $out/plain_$name.json > $prof/${tag}_bench_unprofiled_$name.json || true
   echo "[collect] plain $name done"
 }
 cd $root
-python3 $root/bench.py > $out/plain_default.json 2> $out/plain_default.err || echo "default run failed"
+python3 $root/bench.py --full > $out/plain_default.json 2> $out/plain_default.err || echo "default run failed"
 grep '^{' $out/plain_default.json > $prof/${tag}_bench_default_run.json || true
 echo "[collect] default run done"
 run_plain cfg2 --config cfg2 --no-cpu-baseline
