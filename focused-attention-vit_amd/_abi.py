@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfavit.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "favit.h")
 
 F32, BF16, FP8 = 0, 1, 2
+F32X3 = 3        # favit_gemm_t.in_dtype only: fp32 operands, three-pass split-bf16 product (include/favit.h)
 E4M3, E5M2 = 0, 1
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_SAVEGRAD, ACT_MULAUX = 0, 1, 2, 3, 4
 ERR_INVALID, ERR_UNSUPPORTED, ERR_ALIGN, ERR_LAUNCH = -1, -2, -3, -4

@@ -11,7 +11,8 @@
 //   * "glds": 128x128 tile, direct-to-LDS double buffer (small and batched problems)
 //   * the register-staged 128x128 kernel (any shape / alignment; the fallback)
 // and two exact-fp32 kernels (the parity mode): "p4f", the p4 structure with v_mfma_f32_32x32x2_f32 for the large
-// problems, and the register-staged 128x128 one.  In the 128x128 kernels a 256-thread workgroup
+// problems, and the register-staged 128x128 one; "p4x3" is p4f with the inner product as a three-pass split-bf16
+// product (in_dtype = FAVIT_F32X3, the fp32x3 mode).  In the 128x128 kernels a 256-thread workgroup
 // (4 waves, 2x2) owns the tile, each wave a 64x64 sub-tile; operands are consumed from LDS as
 // MFMA fragments:
 //   bf16 : v_mfma_f32_16x16x32_bf16, BK = 64.
@@ -2536,6 +2537,32 @@ __global__ __launch_bounds__(NTHREADS) void gemm_f32_kernel(KParams p) {
 //   mn-major image: [16 k][W] floats (W = 256 / 128), k-rows whose bit 2 is set rotated by 32 words so that the two
 //                   lane halves of a fragment read (k-rows 8t + s and 8t + 4 + s) hit different banks.
 // --------------------------------------------------------------------------------------
+// fp32x3 operand split (include/favit.h, FAVIT_F32X3): hi = bf16_rne(x), lo = bf16_rne(x - float(hi)).  Both
+// conversions are v_cvt_pk_bf16_f32 (round to nearest even, two elements per instruction); float(hi) is a shift / a
+// mask of the packed pair, the subtraction is exact in fp32.  Five VALU instructions per pair of elements beside the
+// MFMAs; the empty asm keeps the compiler from converting the low element a second time for its float(hi), and the
+// two subtractions are spelled differently (x - h and fma(-1, h, x): the same value, the same v_sub_f32) so that the
+// SLP vectoriser does not fuse them into a v_pk_add_f32, which is slow beside MFMAs.
+__device__ __forceinline__ void split_bf16_pair(float x0, float x1, uint32_t& hi, uint32_t& lo) {
+  const bf16x2 hp = {(bf16_t)x0, (bf16_t)x1};
+  hi = __builtin_bit_cast(uint32_t, hp);
+  asm("" : "+v"(hi));
+  const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
+  const bf16x2 lp = {(bf16_t)(x0 - h0), (bf16_t)__builtin_fmaf(-1.0f, h1, x1)};
+  lo = __builtin_bit_cast(uint32_t, lp);
+}
+
+__device__ __forceinline__ void split_bf16x8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
+  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+  uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
+  split_bf16_pair(x0[0], x0[1], h0, l0);
+  split_bf16_pair(x0[2], x0[3], h1, l1);
+  split_bf16_pair(x1[0], x1[1], h2, l2);
+  split_bf16_pair(x1[2], x1[3], h3, l3);
+  hi = __builtin_bit_cast(bf16x8, (u32x4){h0, h1, h2, h3});
+  lo = __builtin_bit_cast(bf16x8, (u32x4){l0, l1, l2, l3});
+}
+
 template <int W>
 __device__ __forceinline__ const char* glds_src_f32_mn(const char* base, long ld, long i0, long I, long k0, int q, int lane) {
   constexpr int LPR = W / 4;                           // lanes (16-byte chunks) per k-row
@@ -2548,7 +2575,7 @@ __device__ __forceinline__ const char* glds_src_f32_mn(const char* base, long ld
   return base + ((k0 + krow) * ld + i) * 4;
 }
 
-template <bool AK, bool BKM, int TBM, int NW>
+template <bool AK, bool BKM, int TBM, int NW, bool X3 = false>
 __device__ __forceinline__ void p4f_body(const KParams& p, int tile, int split) {
   static_assert(TBM == 256 || TBM == 128, "256x128 tiles, or 128x128 ones where those balance better");
   // NW = 4 (2x2 waves of 128 / 64 rows, 174-182 VGPRs, two waves per SIMD from two workgroups) was measured: 8192^3
@@ -2634,40 +2661,79 @@ __device__ __forceinline__ void p4f_body(const KParams& p, int tile, int split) 
     if (kt + 2 < nk) issue(cur >= 1 ? cur - 1 : 2);
     const char* la = smem + cur * STAGE;
     const char* lb = la + A_BYTES;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f32x4 a[NI], b[2];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
+    if constexpr (X3) {
+      // fp32x3: the whole 16-k stage is ONE v_mfma_f32_32x32x16_bf16 k-step.  A lane's eight k values are the two
+      // chunks the exact loop below reads in its two groups (k = 4 h + s and 8 + 4 h + s, s = 0..3; A and B permute k
+      // identically), so the LDS reads -- and their bank behaviour -- are p4f's.  The fragments are split in registers.
+      auto frag_a = [&](int t, int i) __attribute__((always_inline)) -> f32x4 {
         if (AK) {
           const int row = wr * WR + i * 32 + l31;
-          a[i] = *reinterpret_cast<const f32x4*>(la + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
-        } else {
-          const float* f = reinterpret_cast<const float*>(la) + (8 * t + 4 * h) * TBM + ((wr * WR + i * 32 + l31 + 32 * h) & (TBM - 1));
-          a[i] = (f32x4){f[0], f[TBM], f[2 * TBM], f[3 * TBM]};
+          return *reinterpret_cast<const f32x4*>(la + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
         }
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
+        const float* f = reinterpret_cast<const float*>(la) + (8 * t + 4 * h) * TBM + ((wr * WR + i * 32 + l31 + 32 * h) & (TBM - 1));
+        return (f32x4){f[0], f[TBM], f[2 * TBM], f[3 * TBM]};
+      };
+      auto frag_b = [&](int t, int j) __attribute__((always_inline)) -> f32x4 {
         if (BKM) {
           const int row = wc * 64 + j * 32 + l31;
-          b[j] = *reinterpret_cast<const f32x4*>(lb + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
-        } else {
-          const float* f = reinterpret_cast<const float*>(lb) + (8 * t + 4 * h) * 128 + ((wc * 64 + j * 32 + l31 + 32 * h) & 127);
-          b[j] = (f32x4){f[0], f[128], f[256], f[384]};
+          return *reinterpret_cast<const f32x4*>(lb + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
         }
-      }
-      // (s_setprio 1 around the 8 NI MFMAs of a group, so that the arbiter stays with one wave: 8192^3 132.5 -> 108.6 TF)
+        const float* f = reinterpret_cast<const float*>(lb) + (8 * t + 4 * h) * 128 + ((wc * 64 + j * 32 + l31 + 32 * h) & 127);
+        return (f32x4){f[0], f[128], f[256], f[384]};
+      };
+      bf16x8 ah[NI], al[NI], bh[2], bl[2];
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int i = 0; i < NI; ++i) {
+        const f32x4 a0 = frag_a(0, i), a1 = frag_a(1, i);
+        split_bf16x8(a0, a1, ah[i], al[i]);
+        if (do_rowsum) rs[i] += ((a0[0] + a0[1]) + (a0[2] + a0[3])) + ((a1[0] + a1[1]) + (a1[2] + a1[3]));   // unsplit values
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) split_bf16x8(frag_b(0, j), frag_b(1, j), bh[j], bl[j]);
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], ah[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[j], ah[i], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[j], al[i], acc[i][j], 0, 0, 0);
+        }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f32x4 a[NI], b[2];
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-          acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0][s], a[i][s], acc[i][0], 0, 0, 0);
-          acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[1][s], a[i][s], acc[i][1], 0, 0, 0);
+          if (AK) {
+            const int row = wr * WR + i * 32 + l31;
+            a[i] = *reinterpret_cast<const f32x4*>(la + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
+          } else {
+            const float* f = reinterpret_cast<const float*>(la) + (8 * t + 4 * h) * TBM + ((wr * WR + i * 32 + l31 + 32 * h) & (TBM - 1));
+            a[i] = (f32x4){f[0], f[TBM], f[2 * TBM], f[3 * TBM]};
+          }
         }
-      if (do_rowsum) {                              // (wave-uniform) bias gradient: the column sums of the mn-major A
 #pragma unroll
-        for (int i = 0; i < NI; ++i) rs[i] += (a[i][0] + a[i][1]) + (a[i][2] + a[i][3]);
+        for (int j = 0; j < 2; ++j) {
+          if (BKM) {
+            const int row = wc * 64 + j * 32 + l31;
+            b[j] = *reinterpret_cast<const f32x4*>(lb + row * 64 + (((2 * t + h) ^ ksw32(row)) << 4));
+          } else {
+            const float* f = reinterpret_cast<const float*>(lb) + (8 * t + 4 * h) * 128 + ((wc * 64 + j * 32 + l31 + 32 * h) & 127);
+            b[j] = (f32x4){f[0], f[128], f[256], f[384]};
+          }
+        }
+        // (s_setprio 1 around the 8 NI MFMAs of a group, so that the arbiter stays with one wave: 8192^3 132.5 -> 108.6 TF)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int i = 0; i < NI; ++i) {
+            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0][s], a[i][s], acc[i][0], 0, 0, 0);
+            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[1][s], a[i][s], acc[i][1], 0, 0, 0);
+          }
+        if (do_rowsum) {                              // (wave-uniform) bias gradient: the column sums of the mn-major A
+#pragma unroll
+          for (int i = 0; i < NI; ++i) rs[i] += (a[i][0] + a[i][1]) + (a[i][2] + a[i][3]);
+        }
       }
     }
     cur = cur == 2 ? 0 : cur + 1;
@@ -2718,6 +2784,15 @@ __global__ __launch_bounds__(P4_THREADS, 4) void gemm_f32_p4_kernel(KParams p) {
   int tile, split;
   tile_and_split(p, tile, split);
   p4f_body<AK, BKM, TBM, 8>(p, tile, split);
+}
+
+// fp32x3 kernel "p4x3": p4f's ring, images and epilogue; per 32x32 accumulator block and stage three
+// v_mfma_f32_32x32x16_bf16 (hi*hi, hi_a*lo_b, lo_a*hi_b) in place of eight v_mfma_f32_32x32x2_f32.
+template <bool AK, bool BKM, int TBM>
+__global__ __launch_bounds__(P4_THREADS, 4) void gemm_f32x3_p4_kernel(KParams p) {
+  int tile, split;
+  tile_and_split(p, tile, split);
+  p4f_body<AK, BKM, TBM, 8, true>(p, tile, split);
 }
 
 __global__ void zero_c_kernel(float* C, long M, long N, long ldc, long sCo, long sCi, int batch_inner) {
@@ -2782,8 +2857,18 @@ extern "C" void favit_probe_buffer(void* buf) { g_probe_buffer = reinterpret_cas
 
 extern "C" const char* favit_gemm_last_kernel(void) { return g_last_kernel; }
 
-extern "C" int favit_gemm(const favit_gemm_t* g, void* stream) {
-  if (!g || !g->A || !g->B || !g->C) return FAVIT_ERR_INVALID;
+extern "C" int favit_gemm(const favit_gemm_t* g_in, void* stream) {
+  if (!g_in || !g_in->A || !g_in->B || !g_in->C) return FAVIT_ERR_INVALID;
+  // FAVIT_F32X3 is FAVIT_F32 in every respect (storage, epilogue, split-K plan) except the inner product of the DMA
+  // kernel: the problem is planned as an exact-fp32 one and x3 picks gemm_f32x3_p4_kernel where gemm_f32_p4_kernel
+  // would run; every other problem runs the exact kernel it runs under FAVIT_F32.
+  const bool x3 = g_in->in_dtype == FAVIT_F32X3;
+  favit_gemm_t g_f32;
+  if (x3) {
+    g_f32 = *g_in;
+    g_f32.in_dtype = FAVIT_F32;
+  }
+  const favit_gemm_t* g = x3 ? &g_f32 : g_in;
   if (g->M <= 0 || g->N <= 0 || g->K < 0) return FAVIT_ERR_INVALID;
   if (g->in_dtype != FAVIT_F32 && g->in_dtype != FAVIT_BF16 && g->in_dtype != FAVIT_FP8) return FAVIT_ERR_INVALID;
   if (g->out_dtype != FAVIT_F32 && g->out_dtype != FAVIT_BF16) return FAVIT_ERR_INVALID;
@@ -3088,6 +3173,22 @@ extern "C" int favit_gemm(const favit_gemm_t* g, void* stream) {
     KParams kf = kp;
     kf.ntiles = (int)t4f;
     const dim3 gridf((unsigned)t4f, (unsigned)splits, 1u);
+    if (x3) {
+      if (f32_tbm == 256) {
+        switch (layout) {
+          case 3: return launch_p4(gemm_f32x3_p4_kernel<true, true, 256>, kf, gridf, st, "p4x3");
+          case 2: return launch_p4(gemm_f32x3_p4_kernel<true, false, 256>, kf, gridf, st, "p4x3");
+          case 1: return launch_p4(gemm_f32x3_p4_kernel<false, true, 256>, kf, gridf, st, "p4x3");
+          default: return launch_p4(gemm_f32x3_p4_kernel<false, false, 256>, kf, gridf, st, "p4x3");
+        }
+      }
+      switch (layout) {
+        case 3: return launch_p4(gemm_f32x3_p4_kernel<true, true, 128>, kf, gridf, st, "p4x3_128");
+        case 2: return launch_p4(gemm_f32x3_p4_kernel<true, false, 128>, kf, gridf, st, "p4x3_128");
+        case 1: return launch_p4(gemm_f32x3_p4_kernel<false, true, 128>, kf, gridf, st, "p4x3_128");
+        default: return launch_p4(gemm_f32x3_p4_kernel<false, false, 128>, kf, gridf, st, "p4x3_128");
+      }
+    }
     if (f32_tbm == 256) {
       switch (layout) {
         case 3: return launch_p4(gemm_f32_p4_kernel<true, true, 256>, kf, gridf, st, "p4f");

@@ -122,23 +122,36 @@ def join_side_stream() -> None:
 
 
 def set_compute_dtype(d) -> None:
-    """'fp32' (exact f32 MFMA path, the parity mode), 'bf16' (bf16 MFMA, fp32 accumulate) or 'fp8'
+    """'fp32' (exact f32 MFMA path, the parity mode), 'fp32x3' (fp32 storage and fp32 everywhere except the inner
+    product of the large GEMMs, which is the three-pass split-bf16 product FAVIT_F32X3 of include/favit.h: about
+    4e-6 per GEMM against 4e-7, inside every fp32-mode tolerance), 'bf16' (bf16 MFMA, fp32 accumulate) or 'fp8'
     (BASELINE.json configs[3]: the nn.Linear GEMMs of the encoder blocks run on fp8 MFMA -- e4m3
     activations / weights, e5m2 gradients, per-tensor scales taken on the device -- everything else as
-    in 'bf16'; patch embedding and classifier head stay bf16)."""
-    fp8 = False
+    in 'bf16'; patch embedding and classifier head stay bf16).
+    With FAVIT_FP32_GEMM=x3 in the environment (read at each call) 'fp32' selects 'fp32x3': unlike the
+    kernel-selection switches this one changes results."""
+    fp8 = x3 = False
     if isinstance(d, str):
         fp8 = d == "fp8"
-        d = {"fp32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16,
-             "fp8": torch.bfloat16}[d]
+        x3 = d == "fp32x3"
+        d = {"fp32": torch.float32, "float32": torch.float32, "fp32x3": torch.float32, "bf16": torch.bfloat16,
+             "bfloat16": torch.bfloat16, "fp8": torch.bfloat16}[d]
     if d not in (torch.float32, torch.bfloat16):
-        raise ValueError("compute dtype must be fp32, bf16 or fp8")
+        raise ValueError("compute dtype must be fp32, fp32x3, bf16 or fp8")
+    if d == torch.float32 and os.environ.get("FAVIT_FP32_GEMM") == "x3":
+        x3 = True
     _STATE["cdt"] = d
     _STATE["fp8"] = fp8
+    _STATE["x3"] = x3
+    K.set_f32_gemm_split(x3)
 
 
 def get_compute_mode() -> str:
-    return "fp8" if _STATE.get("fp8") else ("bf16" if _STATE["cdt"] == torch.bfloat16 else "fp32")
+    if _STATE.get("fp8"):
+        return "fp8"
+    if _STATE["cdt"] == torch.bfloat16:
+        return "bf16"
+    return "fp32x3" if _STATE.get("x3") else "fp32"
 
 
 def get_compute_dtype() -> torch.dtype:

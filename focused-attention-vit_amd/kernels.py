@@ -17,6 +17,14 @@ from ._abi import ACT_DGELU, ACT_GELU, ACT_NONE, BF16, F32, GemmDesc, SdpaDesc
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
+# in_dtype that gemm() gives a problem with fp32 operands: F32 (exact f32 MFMA) or F32X3 (the split-bf16 product of the
+# 'fp32x3' compute mode).  functional.set_compute_dtype owns it; small_linear_* and the attention kernels never see it.
+_F32_GEMM = {"in_dtype": F32}
+
+
+def set_f32_gemm_split(on: bool) -> None:
+    _F32_GEMM["in_dtype"] = _abi.F32X3 if on else F32
+
 # bench.py sets this to a list to time every favit_gemm launch with HIP events recorded on the
 # stream the kernel is launched on (torch's current stream): entries are
 # (start_event, end_event, algorithmic_flops, kernel_key, shape, kernel family the library dispatched to).
@@ -63,8 +71,9 @@ def _st():
 def gemm(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_kmajor=True, b_kmajor=True, bias=None, act=ACT_NONE,
          aux_in=None, ld_aux_in=0, aux_out=None, ld_aux_out=0, residual=None, ld_res=0, a_rowsum=None,
          accumulate=False, alpha=1.0, batch=1, batch_inner=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), split_k=0,
-         a_off=0, b_off=0, c_off=0, dropout_p=0.0, dropout_seed=0, scale_a=None, scale_b=None):
+         a_off=0, b_off=0, c_off=0, dropout_p=0.0, dropout_seed=0, scale_a=None, scale_b=None, in_dtype=None):
     """C[m,n] = epilogue(alpha * sum_k A[m,k] B[n,k]).  Offsets/strides are in elements.
+    in_dtype (fp32 operands only): _abi.F32 or _abi.F32X3 for this call, whatever the compute mode says.
     float8 operands (A e4m3 / e5m2, B e4m3; both k-major): scale_a / scale_b are the device scalars
     written by fp8_quantize."""
     require_gpu(A, B, Cc)
@@ -93,6 +102,10 @@ def gemm(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_kmajor=True, b_kmajor=True, bias
     d.batch, d.batch_inner = batch, batch_inner
     d.a_kmajor, d.b_kmajor = int(a_kmajor), int(b_kmajor)
     d.in_dtype, d.out_dtype = (_abi.FP8 if fp8 else dt(A)), dt(Cc)
+    if d.in_dtype == F32:
+        d.in_dtype = _F32_GEMM["in_dtype"] if in_dtype is None else in_dtype
+    elif in_dtype is not None:
+        raise TypeError("in_dtype selects the product of fp32 operands only")
     if fp8:
         d.fp8_fmt = 1 if A.dtype == torch.float8_e5m2 else 0
         d.scale_a = scale_a.data_ptr() if scale_a is not None else None
@@ -114,7 +127,7 @@ def gemm(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_kmajor=True, b_kmajor=True, bias
     e0.record()
     _abi.check(_abi.lib().favit_gemm(C.byref(d), _st()), "favit_gemm")
     e1.record()
-    key = ("fp8" if fp8 else "bf16" if A.dtype == torch.bfloat16 else "f32") + ("_K" if a_kmajor else "_M") + ("K" if b_kmajor else "M") + \
+    key = ("fp8" if fp8 else "bf16" if A.dtype == torch.bfloat16 else "f32x3" if d.in_dtype == _abi.F32X3 else "f32") + ("_K" if a_kmajor else "_M") + ("K" if b_kmajor else "M") + \
           ("_obf16" if Cc.dtype == torch.bfloat16 else "_of32")
     GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch, key, (M, N, K, batch), _abi.lib().favit_gemm_last_kernel().decode()))
 

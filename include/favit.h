@@ -31,7 +31,9 @@ extern "C" {
 #define FAVIT_ABI_VERSION 8
 #define FAVIT_FP8_AMAX_SLOTS 256   /* partial maxima per tensor with delayed fp8 scaling (favit_fp8_quantize) */
 
-enum { FAVIT_F32 = 0, FAVIT_BF16 = 1, FAVIT_FP8 = 2 };
+/* FAVIT_F32X3: valid only as favit_gemm_t.in_dtype (see favit_gemm_t); additive in ABI 8 (the value was
+ * FAVIT_ERR_INVALID before). */
+enum { FAVIT_F32 = 0, FAVIT_BF16 = 1, FAVIT_FP8 = 2, FAVIT_F32X3 = 3 };
 /* OCP 8-bit float formats of gfx950 (NOT the MI300X fnuz encodings) */
 enum { FAVIT_E4M3 = 0, FAVIT_E5M2 = 1 };
 
@@ -97,6 +99,16 @@ int favit_set_health_word(uint32_t* device_words);
  *   be E4M3), both k-major, K a multiple of 64 and 16-byte aligned rows, batch = 1; the true operands
  *   are A*scale_a[0] and B*scale_b[0] (device scalars written by favit_fp8_quantize, NULL = 1), i.e.
  *   v = alpha*scale_a*scale_b*acc.  aux_in (DGELU) is bf16 in this mode.
+ * in_dtype = FAVIT_F32X3: operands are fp32 in memory and out_dtype is FAVIT_F32, exactly as for FAVIT_F32; only
+ *   the inner product differs.  It is the three-pass split product on the bf16 MFMA:
+ *       hi = bf16_rne(x),  lo = bf16_rne(x - float(hi))          (round to nearest even, both parts)
+ *       acc += hi_a*hi_b + hi_a*lo_b + lo_a*hi_b                 (fp32 MFMA accumulators)
+ *   The dropped lo_a*lo_b term and the residual of the split are ~2^-17 relative: rel-L2 against an fp64 product
+ *   about 4e-6 at every K, against 4e-7 for FAVIT_F32.  Epilogue, a_rowsum (which sums the UNSPLIT fp32 values),
+ *   split_k and accumulate behave as for FAVIT_F32.  It is a request, not a guarantee: a problem the split kernel
+ *   does not cover (batched, K not a multiple of 16, operands not 16-byte aligned, too few tiles to fill the
+ *   device) runs the exact-fp32 kernel it runs under FAVIT_F32, which is never less accurate;
+ *   favit_gemm_last_kernel() says which one ran.
  * ---------------------------------------------------------------------------------- */
 typedef struct favit_gemm_t {
   const void* A;
@@ -126,7 +138,9 @@ typedef struct favit_gemm_t {
 
 int favit_gemm(const favit_gemm_t* g, void* stream);
 /* Diagnostic: the kernel family ("p4" 256x128 tiles, "p7" 256x256, "pp" ping-pong, "s64" 64-row, "t128"
- * 128x128 / exact-fp32) the calling host thread's last favit_gemm dispatched to.  Static string, never NULL. */
+ * 128x128 / exact-fp32, "p4f" / "p4f128" the exact-fp32 DMA kernel with 256- / 128-row tiles, "p4x3" / "p4x3_128"
+ * the FAVIT_F32X3 split-bf16 form of those two) the calling host thread's last favit_gemm dispatched to.  Static
+ * string, never NULL. */
 const char* favit_gemm_last_kernel(void);
 
 /* LayerNorm fused into a small-M forward GEMM (v7):  C = epilogue( LN(x; gamma, beta, eps) . B^T )  in ONE launch, for

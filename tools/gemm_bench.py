@@ -28,7 +28,9 @@ def run(name, fn, flops):
     us = e0.elapsed_time(e1) * 1e3 / reps
     print(f"{name:28s} {us:9.1f} us  {flops / us / 1e6:8.1f} TFLOP/s", flush=True)
 
-bf = torch.float32 if os.environ.get("F32") else torch.bfloat16        # F32=1: the exact-fp32 kernels on the same shapes
+x3 = bool(os.environ.get("X3"))                                       # X3=1: fp32 operands, the fp32x3 split-bf16 kernels
+bf = torch.float32 if os.environ.get("F32") or x3 else torch.bfloat16  # F32=1: the exact-fp32 kernels on the same shapes
+K.set_f32_gemm_split(x3)
 def rnd(*s, dt=bf): return torch.randn(*s, device=dev).to(dt)
 x = rnd(T, D); h = rnd(T, 4 * D)
 wqkv = rnd(3 * D, D); w1 = rnd(4 * D, D); w2 = rnd(D, 4 * D); wp = rnd(D, D)
