@@ -64,10 +64,13 @@ __device__ __forceinline__ int clip8(int v) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// horizontal pass: tmp[b][y][x][c] for crop rows y < ch and resized columns x < rw that the output window needs
-__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp,
-                                                         const int* __restrict__ prm, int Hs, int Ws, int C, int ch_max,
-                                                         int S) {
+// horizontal pass: tmp[b][y][x][c] for crop rows y < ch and resized columns x < rw that the output window needs.
+// RAGGED: the images lie back to back in one packed buffer and desc [B,3] (int64) holds byte offset, Hs, Ws of each;
+// this pass is the only one that reads the source, so it is the only one that differs.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ desc,
+                                                         uint8_t* __restrict__ tmp, const int* __restrict__ prm, int Hs,
+                                                         int Ws, int C, int ch_max, int S) {
   const int b = blockIdx.z, y = blockIdx.y;
   const int x = blockIdx.x * 256 + threadIdx.x;       // output-window column
   const int* p = prm + b * 12;
@@ -79,7 +82,15 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restri
   Taps t;
   pil_taps(cw, rw, xr, t);
   const int sy = top + y - pad;
-  const uint8_t* img = src + (long)b * Hs * Ws * C;
+  const uint8_t* img;
+  if (RAGGED) {
+    const int64_t* d = desc + (long)b * 3;
+    img = src + d[0];
+    Hs = (int)d[1];
+    Ws = (int)d[2];
+  } else {
+    img = src + (long)b * Hs * Ws * C;
+  }
   int acc[4] = {1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1)};
   for (int k = 0; k < t.n; ++k) {
     const int xc = t.xmin + k;                        // column inside the crop
@@ -122,6 +133,17 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
   }
 }
 
+// the vertical pass is shared: it reads tmp and the parameter rows only
+int launch_vertical(const uint8_t* tmp, float* out, uint8_t* out_u8, const int32_t* params, int32_t B, int32_t C,
+                    int32_t ch_max, int32_t S, const float* mean, const float* std, hipStream_t st) {
+  const dim3 gv((unsigned)((S + 255) / 256), (unsigned)S, (unsigned)B);
+  const float3 m = make_float3(mean[0], mean[C > 1 ? 1 : 0], mean[C > 2 ? 2 : 0]);
+  const float3 sd = make_float3(std[0], std[C > 1 ? 1 : 0], std[C > 2 ? 2 : 0]);
+  hipLaunchKernelGGL(resample_v_kernel, gv, dim3(256), 0, st, tmp, out, out_u8, params, C, ch_max, S, m, sd);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
 }  // namespace
 
 extern "C" int favit_image_transform(const uint8_t* src, uint8_t* tmp, float* out, uint8_t* out_u8, const int32_t* params,
@@ -132,12 +154,24 @@ extern "C" int favit_image_transform(const uint8_t* src, uint8_t* tmp, float* ou
   if (C < 1 || C > 4) return FAVIT_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   const dim3 gh((unsigned)((S + 255) / 256), (unsigned)ch_max, (unsigned)B);
-  hipLaunchKernelGGL(resample_h_kernel, gh, dim3(256), 0, st, src, tmp, params, Hs, Ws, C, ch_max, S);
+  hipLaunchKernelGGL(resample_h_kernel<false>, gh, dim3(256), 0, st, src, (const int64_t*)nullptr, tmp, params, Hs, Ws, C,
+                     ch_max, S);
   FAVIT_CHECK_LAUNCH();
-  const dim3 gv((unsigned)((S + 255) / 256), (unsigned)S, (unsigned)B);
-  const float3 m = make_float3(mean[0], mean[C > 1 ? 1 : 0], mean[C > 2 ? 2 : 0]);
-  const float3 sd = make_float3(std[0], std[C > 1 ? 1 : 0], std[C > 2 ? 2 : 0]);
-  hipLaunchKernelGGL(resample_v_kernel, gv, dim3(256), 0, st, tmp, out, out_u8, params, C, ch_max, S, m, sd);
+  return launch_vertical(tmp, out, out_u8, params, B, C, ch_max, S, mean, std, st);
+}
+
+// Mixed-size batch: src is one packed buffer, src_desc [B,3] (device, int64) = byte offset, Hs, Ws per image.  The
+// descriptors live on the device and are not visible here: the caller guarantees offset + Hs*Ws*C <= size of src
+// (data.py checks it on the host arrays before the upload).
+extern "C" int favit_image_transform_ragged(const uint8_t* src, const int64_t* src_desc, uint8_t* tmp, float* out,
+                                            uint8_t* out_u8, const int32_t* params, int32_t B, int32_t C, int32_t ch_max,
+                                            int32_t S, const float* mean, const float* std, void* stream) {
+  if (!src || !src_desc || !tmp || !out || !params || !mean || !std || B <= 0 || S <= 0 || ch_max <= 0)
+    return FAVIT_ERR_INVALID;
+  if (C < 1 || C > 4) return FAVIT_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+  const dim3 gh((unsigned)((S + 255) / 256), (unsigned)ch_max, (unsigned)B);
+  hipLaunchKernelGGL(resample_h_kernel<true>, gh, dim3(256), 0, st, src, src_desc, tmp, params, 0, 0, C, ch_max, S);
   FAVIT_CHECK_LAUNCH();
-  return FAVIT_OK;
+  return launch_vertical(tmp, out, out_u8, params, B, C, ch_max, S, mean, std, st);
 }

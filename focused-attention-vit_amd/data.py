@@ -38,8 +38,81 @@ def _resized_size(h: int, w: int, size: int) -> Tuple[int, int]:
     return int(size * h / w), size
 
 
+class RaggedBatch:
+    """A batch of HWC uint8 images of different sizes, packed back to back (an ImageFolder batch).
+
+    bytes   : uint8 1-D torch tensor, on the host or on the device
+    offsets : int64 [B] byte offset of each image inside ``bytes``        (always HOST numpy arrays: the descriptors
+    heights, widths : int32 [B]                                            are validated without touching the device)
+    channels: bytes per pixel (3 for the readers of datasets.py)
+    """
+
+    def __init__(self, bytes, offsets, heights, widths, channels: int = 3):
+        self.bytes = bytes if torch.is_tensor(bytes) else torch.as_tensor(np.asarray(bytes))
+        self.offsets = np.asarray(offsets, dtype=np.int64)
+        self.heights = np.asarray(heights, dtype=np.int32)
+        self.widths = np.asarray(widths, dtype=np.int32)
+        self.channels = int(channels)
+
+    @classmethod
+    def from_images(cls, images: Sequence[np.ndarray]) -> "RaggedBatch":
+        """Pack a list of HWC uint8 arrays (all with the same channel count)."""
+        if len(images) == 0:
+            raise ValueError("RaggedBatch.from_images: empty list")
+        imgs = [np.asarray(im) for im in images]
+        ch = imgs[0].shape[2] if imgs[0].ndim == 3 else 0
+        for i, im in enumerate(imgs):
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != ch:
+                raise TypeError(f"RaggedBatch.from_images: image {i} is not a uint8 [H, W, {ch}] array")
+        sizes = np.array([im.size for im in imgs], dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        buf = np.empty(int(sizes.sum()), dtype=np.uint8)
+        for im, o, n in zip(imgs, offsets, sizes):
+            buf[o:o + n] = im.reshape(-1)
+        return cls(torch.from_numpy(buf), offsets, [im.shape[0] for im in imgs], [im.shape[1] for im in imgs], ch)
+
+    def __len__(self) -> int:
+        return len(self.offsets)
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.bytes.is_cuda
+
+    def image(self, b: int) -> np.ndarray:
+        """Image b as a HWC array (host batches)."""
+        h, w, o = int(self.heights[b]), int(self.widths[b]), int(self.offsets[b])
+        return self.bytes[o:o + h * w * self.channels].cpu().numpy().reshape(h, w, self.channels)
+
+    def to(self, device, non_blocking: bool = False) -> "RaggedBatch":
+        return RaggedBatch(self.bytes.to(device, non_blocking=non_blocking), self.offsets.copy(), self.heights.copy(),
+                           self.widths.copy(), self.channels)
+
+    def record_stream(self, stream) -> None:
+        self.bytes.record_stream(stream)
+
+    def descriptors(self) -> np.ndarray:
+        """int64 [B,3] rows (byte offset, Hs, Ws) for favit_image_transform_ragged.  Every row is checked against the
+        size of ``bytes`` here, on the host arrays: the kernel trusts them."""
+        B = len(self.offsets)
+        if self.bytes.dtype != torch.uint8 or self.bytes.dim() != 1:
+            raise TypeError("RaggedBatch.bytes must be a 1-D uint8 tensor")
+        if B == 0 or self.heights.shape != (B,) or self.widths.shape != (B,) or self.offsets.shape != (B,):
+            raise ValueError("RaggedBatch: offsets, heights and widths must be non-empty [B] arrays of one length")
+        if not 1 <= self.channels <= 4:
+            raise ValueError(f"RaggedBatch: {self.channels} channels (1..4 supported)")
+        d = np.stack([self.offsets, self.heights.astype(np.int64), self.widths.astype(np.int64)], axis=1)
+        end = d[:, 0] + d[:, 1] * d[:, 2] * self.channels
+        bad = (d[:, 0] < 0) | (d[:, 1] <= 0) | (d[:, 2] <= 0) | (end > self.bytes.numel())
+        if bad.any():
+            b = int(np.argmax(bad))
+            raise ValueError(f"RaggedBatch: image {b} (offset {int(d[b, 0])}, {int(d[b, 1])}x{int(d[b, 2])}x{self.channels}) "
+                             f"does not lie inside the {self.bytes.numel()}-byte buffer")
+        return np.ascontiguousarray(d)
+
+
 class DeviceTransform:
-    """One of the reference's transform stacks, run by favit_image_transform.
+    """One of the reference's transform stacks, run by favit_image_transform (favit_image_transform_ragged for a
+    RaggedBatch of mixed-size images).
 
     kind: 'cifar10_train'  RandomCrop(32, padding=4) -> RandomHorizontalFlip -> Resize(S) -> ToTensor -> Normalize
           'imagenet_train' RandomResizedCrop(S) -> RandomHorizontalFlip -> ToTensor -> Normalize
@@ -57,7 +130,23 @@ class DeviceTransform:
         self.rng = np.random.RandomState(seed)
 
     # ---- per-image parameter rows (see include/favit.h: favit_image_transform) ----
-    def params(self, B: int, H: int, W: int) -> np.ndarray:
+    def params(self, B: int, H, W) -> np.ndarray:
+        """H, W: the source size, scalars for a uniform batch or [B] arrays for a ragged one (every row is then drawn
+        from that image's own size, image by image)."""
+        if np.ndim(H) == 0 and np.ndim(W) == 0:
+            p = self._rows(B, int(H), int(W))
+        else:
+            Hs, Ws = np.broadcast_to(np.asarray(H), (B,)), np.broadcast_to(np.asarray(W), (B,))
+            p = np.zeros((B, 12), dtype=np.int32)
+            for b in range(B):
+                try:
+                    p[b] = self._rows(1, int(Hs[b]), int(Ws[b]))[0]
+                except ValueError as e:
+                    raise ValueError(f"image {b} ({int(Hs[b])}x{int(Ws[b])}): {e}") from None
+        self.check_params(p)
+        return p
+
+    def _rows(self, B: int, H: int, W: int) -> np.ndarray:
         S, r = self.S, self.rng
         p = np.zeros((B, 12), dtype=np.int32)
         if self.kind == "cifar10_train":
@@ -103,7 +192,6 @@ class DeviceTransform:
             rh, rw = _resized_size(H, W, int(S * 1.14))
             p[:, 2], p[:, 3], p[:, 5], p[:, 6] = H, W, rh, rw
             p[:, 7], p[:, 8] = int(round((rh - S) / 2.0)), int(round((rw - S) / 2.0))
-        self.check_params(p)
         return p
 
     MAX_TAPS = 64          # csrc/image.hip: filter taps per output position the resampling kernels hold
@@ -122,8 +210,11 @@ class DeviceTransform:
                                  f"({int(c[b])} -> {int(r[b])} pixels): {int(taps[b])} filter taps exceed the kernels' "
                                  f"{cls.MAX_TAPS}; resize such sources on the host first")
 
-    def __call__(self, batch_u8: torch.Tensor, params: Optional[np.ndarray] = None, want_bytes: bool = False):
-        """batch_u8: uint8 [B, H, W, C] on the GPU -> fp32 [B, C, S, S] (and the resized bytes if want_bytes)."""
+    def __call__(self, batch_u8, params: Optional[np.ndarray] = None, want_bytes: bool = False):
+        """batch_u8: uint8 [B, H, W, C] on the GPU, or a RaggedBatch whose bytes are on the GPU
+        -> fp32 [B, C, S, S] (and the resized bytes if want_bytes)."""
+        if isinstance(batch_u8, RaggedBatch):
+            return self._call_ragged(batch_u8, params, want_bytes)
         K.require_gpu(batch_u8)
         if batch_u8.dtype != torch.uint8 or batch_u8.dim() != 4:
             raise TypeError("DeviceTransform expects a uint8 [B, H, W, C] batch")
@@ -143,6 +234,28 @@ class DeviceTransform:
                                                     ch_max, S, self.mean, self.std, K._st()), "favit_image_transform")
         return (out, u8) if want_bytes else out
 
+    def _call_ragged(self, rb: RaggedBatch, params: Optional[np.ndarray], want_bytes: bool):
+        K.require_gpu(rb.bytes)
+        desc = rb.descriptors()                            # host-side bounds check, before anything is uploaded
+        B, Cc, S, dev = len(rb), rb.channels, self.S, rb.bytes.device
+        if params is None:
+            params = self.params(B, rb.heights, rb.widths)
+        else:
+            params = np.asarray(params)
+            if params.shape != (B, 12):
+                raise ValueError(f"params must be [{B}, 12]")
+            self.check_params(params)
+        prm = torch.from_numpy(np.ascontiguousarray(params, dtype=np.int32)).to(dev, non_blocking=True)
+        dsc = torch.from_numpy(desc).to(dev, non_blocking=True)
+        ch_max = int(params[:, 2].max())
+        tmp = torch.empty((B, ch_max, S, Cc), dtype=torch.uint8, device=dev)
+        out = torch.empty((B, Cc, S, S), dtype=torch.float32, device=dev)
+        u8 = torch.empty((B, S, S, Cc), dtype=torch.uint8, device=dev) if want_bytes else None
+        _abi.check(_abi.lib().favit_image_transform_ragged(K._p(rb.bytes), K._p(dsc), K._p(tmp), K._p(out), K._p(u8), K._p(prm),
+                                                           B, Cc, ch_max, S, self.mean, self.std, K._st()),
+                   "favit_image_transform_ragged")
+        return (out, u8) if want_bytes else out
+
 
 def get_transforms(dataset_name: str, img_size: int = 224, seed: int = 0) -> Dict[str, DeviceTransform]:
     """Mirror of the reference's get_transforms (utils/data_utils.py:21-81): {'train', 'test'} device transforms."""
@@ -160,7 +273,7 @@ def get_transforms(dataset_name: str, img_size: int = 224, seed: int = 0) -> Dic
 
 class DeviceLoader:
     """Iterates (images fp32 [B,C,S,S], labels int64 [B]) on the GPU from an iterable of HOST batches
-    (uint8 [B,H,W,C] array / tensor, integer labels).  Batch k+1 is copied (pinned staging buffers, a dedicated
+    (uint8 [B,H,W,C] array / tensor, or a RaggedBatch of mixed-size images; integer labels).  Batch k+1 is copied (pinned staging buffers, a dedicated
     copy stream) and transformed while the consumer computes on batch k: no host-side blocking .to(device)."""
 
     def __init__(self, host_batches: Iterable, transform: DeviceTransform, device: Optional[torch.device] = None,
@@ -184,19 +297,41 @@ class DeviceLoader:
         self.prep_stream = streams.cu_masked_stream(SEGMENTER_CUS, self.dev) if segmenter is not None else None
         self.compute_stream = torch.cuda.Stream(device=self.dev) if segmenter is not None else None
         self._pin = [None, None]
+        self._pin_ragged = [None, None]     # [bytes (capacity of the largest batch seen), labels, copy-done event] per slot
 
     def __len__(self):
         return len(self.src)
 
+    def _stage_ragged_host(self, slot: int, rb: RaggedBatch, labels: torch.Tensor):
+        """Pinned views holding a ragged host batch.  The staging buffers only ever grow (to the largest batch seen), and
+        a buffer is rewritten only after the copy that last read it has finished."""
+        n, B = rb.bytes.numel(), labels.numel()
+        buf = self._pin_ragged[slot]
+        if buf is not None and buf[2] is not None:
+            buf[2].synchronize()
+        if buf is None or buf[0].numel() < n or buf[1].numel() < B:
+            buf = [torch.empty(max(n, buf[0].numel() if buf else 0), dtype=torch.uint8).pin_memory(),
+                   torch.empty(max(B, buf[1].numel() if buf else 0), dtype=torch.int64).pin_memory(), None]
+            self._pin_ragged[slot] = buf
+        buf[0][:n].copy_(rb.bytes)
+        buf[1][:B].copy_(labels)
+        return RaggedBatch(buf[0][:n], rb.offsets, rb.heights, rb.widths, rb.channels), buf[1][:B]
+
     def _stage(self, slot: int, imgs, labels):
-        imgs = torch.as_tensor(np.asarray(imgs)) if not torch.is_tensor(imgs) else imgs
+        ragged = isinstance(imgs, RaggedBatch)
+        if not ragged:
+            imgs = torch.as_tensor(np.asarray(imgs)) if not torch.is_tensor(imgs) else imgs
         labels = torch.as_tensor(np.asarray(labels), dtype=torch.int64) if not torch.is_tensor(labels) else labels.to(torch.int64)
-        if imgs.is_pinned() and labels.is_pinned():
+        if ragged and len(imgs) != labels.numel():
+            raise ValueError(f"RaggedBatch of {len(imgs)} images with {labels.numel()} labels")
+        if (imgs.bytes if ragged else imgs).is_pinned() and labels.is_pinned():
             # The producer already wrote into page-locked memory: no staging copy.  CONTRACT: the asynchronous
             # host-to-device copy reads that memory until the batch has been yielded, so the producer must not
             # rewrite a pinned buffer before the loader has yielded the batch made from it (hand out a fresh or a
             # rotated buffer per batch; bench.py --host-input rotates four).
             src = (imgs, labels)
+        elif ragged:
+            src = self._stage_ragged_host(slot, imgs, labels)
         else:
             buf = self._pin[slot]
             if buf is None or buf[0].shape != imgs.shape or buf[1].shape != labels.shape:
@@ -213,7 +348,7 @@ class DeviceLoader:
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         if src[0] is not imgs:
-            self._pin[slot][2] = ev
+            (self._pin_ragged if ragged else self._pin)[slot][2] = ev
         if self.segmenter is not None:
             # transform + SLIC of this (next) batch now, on a stream of their own, under the consumer's current step
             with torch.cuda.stream(self.prep_stream):

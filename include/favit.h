@@ -325,6 +325,16 @@ int favit_softmax_bwd(const void* P, int p_dtype, const float* dPd, void* dS, in
 int favit_image_transform(const uint8_t* src, uint8_t* tmp, float* out, uint8_t* out_u8, const int32_t* params, int32_t B,
                           int32_t Hs, int32_t Ws, int32_t C, int32_t ch_max, int32_t S, const float* mean,
                           const float* std, void* stream);
+/* The same transform for a batch of images of DIFFERENT sizes (a folder of photographs): src is one packed uint8
+ * buffer of HWC images laid back to back, src_desc int64 [B,3] (device) = byte offset, Hs, Ws of each image.  params,
+ * out, out_u8, mean, std and every byte of arithmetic are those of favit_image_transform (only the horizontal pass
+ * reads the source); reads outside [0,Hs) x [0,Ws) of an image are zero padding, never bytes of its neighbour.
+ * tmp: uint8 [B,ch_max,S,C] workspace = B * ch_max * S * C bytes, ch_max >= every crop height (params[:,2]).
+ * The descriptors are device memory and are NOT validated here: the caller guarantees
+ * 0 <= offset and offset + Hs*Ws*C <= size of src for every row (data.py checks its host arrays before the upload). */
+int favit_image_transform_ragged(const uint8_t* src, const int64_t* src_desc, uint8_t* tmp, float* out,
+                                 uint8_t* out_u8, const int32_t* params, int32_t B, int32_t C, int32_t ch_max,
+                                 int32_t S, const float* mean, const float* std, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * SLIC superpixels on the device: replaces the per-image D2H -> skimage.segmentation.slic -> H2D

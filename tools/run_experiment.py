@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """main.py-equivalent runner (the reference's main.py:64-149 cannot even be imported: three wrong
-import names, main.py:41-43).  Same argument names for the settings that concern the path; the dataset is either a
-.npz file {x_train uint8 [N,H,W,3], y_train, x_test, y_test} or a synthetic one (no downloads: there is no network).
+import names, main.py:41-43).  Same argument names for the settings that concern the path; the dataset is an on-disk
+one (--data_dir: CIFAR-10's binary distribution, or an ImageNet-style train/ + val/ image folder), a .npz file
+{x_train uint8 [N,H,W,3], y_train, x_test, y_test} or a synthetic one.  Nothing is ever downloaded.
 
     python tools/run_experiment.py --experiment mhla --img_size 32 --patch_size 4 --embed_dim 64 --depth 2 \
         --num_heads 4 --epochs 3 --batch_size 64 --results_dir gpurun_out/exp
+    python tools/run_experiment.py --experiment mhla_pretrained --dataset imagenet --data_dir /data/imagenet \
+        --weights vit_b_16.npz --freeze_layers --epochs 5
 """
 import argparse
 import importlib
@@ -52,10 +55,87 @@ def batches(x, y, bs, shuffle, rs):
     return [(x[idx[i:i + bs]], y[idx[i:i + bs]]) for i in range(0, len(x) - bs + 1, bs)]
 
 
-def main():
+SPPP_TRAINABLE = ("head", "latent_proj", "segmentation", "patch_mapper", "pooling")
+
+
+def build_model(pkg, a, classes):
+    """The experiment's model (on the host).  The caller seeds torch first: the model is built seeded."""
+    M = pkg.models
+    kw = dict(img_size=a.img_size, patch_size=a.patch_size, num_classes=classes, embed_dim=a.embed_dim, depth=a.depth,
+              num_heads=a.num_heads, dropout=a.dropout)
+    if a.experiment == "traditional":
+        return M.vit.VisionTransformer(**kw)
+    if a.experiment in ("mhla", "mhla_pretrained"):
+        return M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True, **kw)
+    model = M.sppp_mhla.SPPPViTMHLA(num_superpixels=a.num_superpixels, pooling_type=a.pooling_type,
+                                    window_size=a.window_size, use_mhla=True, **kw)
+    model.segmentation.compactness = a.compactness
+    return model
+
+
+def prepare_pretrained(model, weights=None, freeze_layers=False):
+    """The set-up of the reference's two pre-trained experiments (experiments/mhla_pretrained.py:224-247,
+    experiments/sppp_mhla_pretrained.py:236-259).  weights: a flat state-dict .npz archive (opened without pickle);
+    a key the archive lacks stays as initialised, a key with another shape is an error.  Every latent_proj becomes the
+    identity (eye weight, zero bias).  freeze_layers: every parameter whose name contains none of head / latent_proj /
+    segmentation / patch_mapper / pooling stops training (the last three only occur in the SPPP models, so this is
+    both experiments' rule).  Returns the names of the keys that were loaded."""
+    loaded = []
+    if weights:
+        sd = model.state_dict()
+        with np.load(weights, allow_pickle=False) as arc:
+            for k in arc.files:
+                if k not in sd:
+                    continue
+                v = torch.from_numpy(arc[k])
+                if tuple(v.shape) != tuple(sd[k].shape):
+                    raise ValueError(f"{weights}: {k} has shape {tuple(v.shape)}, the model's is {tuple(sd[k].shape)}")
+                with torch.no_grad():
+                    sd[k].copy_(v)
+                loaded.append(k)
+    with torch.no_grad():
+        for n, mod in model.named_modules():
+            if n.endswith("latent_proj") and isinstance(mod, torch.nn.Linear):
+                torch.nn.init.eye_(mod.weight)
+                torch.nn.init.zeros_(mod.bias)
+    if freeze_layers:
+        for n, p in model.named_parameters():
+            if not any(x in n for x in SPPP_TRAINABLE):
+                p.requires_grad = False
+    return loaded
+
+
+def disk_dataset(pkg, a):
+    """--data_dir: (train batches, test batches, number of classes) from the on-disk readers of datasets.py."""
+    DS = pkg.datasets
+    sub, sub5 = a.subset_size, (None if a.subset_size is None else a.subset_size // 5)
+    if a.dataset == "cifar10":
+        tr, te = DS.Cifar10Binary(a.data_dir, True, sub, a.seed), DS.Cifar10Binary(a.data_dir, False, sub5, a.seed)
+    elif a.dataset == "imagenet":
+        tr_dir, va_dir = os.path.join(a.data_dir, "train"), os.path.join(a.data_dir, "val")
+        if not os.path.isdir(tr_dir) or not os.path.isdir(va_dir):
+            raise FileNotFoundError(f"ImageNet train or validation directory not found in {a.data_dir}")
+        tr, te = DS.ImageFolder(tr_dir, sub, a.seed), DS.ImageFolder(va_dir, sub5, a.seed)
+    else:
+        raise SystemExit("--data_dir needs --dataset cifar10 or imagenet")
+    return (DS.batches(tr, a.batch_size, True, a.seed, num_workers=a.num_workers),
+            DS.batches(te, a.batch_size, False, a.seed, num_workers=a.num_workers), len(tr.classes))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Vision Transformer experiments on the MI355X hot path")
-    ap.add_argument("--experiment", required=True, choices=["traditional", "mhla", "sppp_mhla"])
+    ap.add_argument("--experiment", required=True,
+                    choices=["traditional", "mhla", "sppp_mhla", "mhla_pretrained", "sppp_mhla_pretrained"])
     ap.add_argument("--data", default=None, help=".npz dataset (default: synthetic)")
+    ap.add_argument("--data_dir", default=None,
+                    help="on-disk dataset: with --dataset cifar10 the binary distribution (data_batch_*.bin, test_batch.bin), "
+                         "with --dataset imagenet a directory with train/ and val/ image folders")
+    ap.add_argument("--subset_size", type=int, default=None, help="--data_dir: seeded random subset (test side: a fifth)")
+    ap.add_argument("--num_workers", type=int, default=4, help="--data_dir: image decoding threads (at most 16)")
+    ap.add_argument("--weights", default=None,
+                    help="*_pretrained: flat state-dict .npz archive; keys it lacks stay as initialised")
+    ap.add_argument("--freeze_layers", action="store_true",
+                    help="*_pretrained: train only head, latent_proj and the SPPP components")
     ap.add_argument("--dataset", default="cifar10", choices=["cifar10", "imagenet", "default"], help="transform stack")
     ap.add_argument("--results_dir", default="./results")
     ap.add_argument("--seed", type=int, default=42)
@@ -80,19 +160,28 @@ def main():
                          "group (models.sppp.TokenBucketed; the reference -- and this tool without the flag -- fails on "
                          "such a batch in torch.stack, models/sppp_mhla.py:300; any other count fails in the "
                          "positional encoding, there and here)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    pretrained = a.experiment.endswith("_pretrained")
+    sppp = a.experiment.startswith("sppp_mhla")
 
     pkg = importlib.import_module("focused-attention-vit_amd")
     pkg.set_compute_dtype(a.compute_dtype)
     torch.manual_seed(a.seed)
     rs = np.random.RandomState(a.seed)
-    if a.data:
+    train_src = test_src = None
+    if a.data_dir:
+        train_src, test_src, classes = disk_dataset(pkg, a)
+    elif a.data:
         d = np.load(a.data, allow_pickle=False)
         xtr, ytr, xte, yte = d["x_train"], d["y_train"], d["x_test"], d["y_test"]
     else:
         src = 32 if a.dataset == "cifar10" else a.img_size
         grid = int(round(a.num_superpixels ** 0.5))
-        if a.experiment == "sppp_mhla" and grid * grid == a.num_superpixels:
+        if sppp and grid * grid == a.num_superpixels:
             xtr, ytr = synthetic_blocks_dataset(2048, 10, src, grid, a.seed)
             xte, yte = synthetic_blocks_dataset(512, 10, src, grid, a.seed, sample_seed=a.seed + 1)
             if a.compactness == 0.1:
@@ -105,18 +194,14 @@ def main():
             xtr, ytr = synthetic_dataset(2048, 10, src, a.seed)
             xte, yte = synthetic_dataset(512, 10, src, a.seed)       # same prototypes (same seed), fresh noise below
             xte = np.clip(xte.astype(np.int32) + rs.randint(-10, 11, size=xte.shape), 0, 255).astype(np.uint8)
-    classes = int(max(ytr.max(), yte.max())) + 1
-    M = pkg.models
-    kw = dict(img_size=a.img_size, patch_size=a.patch_size, num_classes=classes, embed_dim=a.embed_dim, depth=a.depth,
-              num_heads=a.num_heads, dropout=a.dropout)
-    if a.experiment == "traditional":
-        model = M.vit.VisionTransformer(**kw)
-    elif a.experiment == "mhla":
-        model = M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True, **kw)
-    else:
-        model = M.sppp_mhla.SPPPViTMHLA(num_superpixels=a.num_superpixels, pooling_type=a.pooling_type,
-                                        window_size=a.window_size, use_mhla=True, **kw)
-        model.segmentation.compactness = a.compactness
+    if train_src is None:
+        classes = int(max(ytr.max(), yte.max())) + 1
+    model = build_model(pkg, a, classes)
+    if pretrained:
+        loaded = prepare_pretrained(model, a.weights, a.freeze_layers)
+        n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
+        print(f"pretrained set-up: {len(loaded)} tensors loaded from {a.weights}; trainable parameters {n_train:,} of "
+              f"{sum(p.numel() for p in model.parameters()):,}")
     model = model.cuda()
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
     opt = pkg.train.FusedAdamW(pkg.train.param_groups(model, lr=a.learning_rate, head_lr=a.head_learning_rate),
@@ -132,8 +217,10 @@ def main():
     # SPPP: the loaders segment batch k + 1 (device SLIC on a CU-masked stream) under the step of batch k; the steps
     # then run on the loader's compute stream, because a CU-masked stream synchronises with the default stream
     seg = getattr(model, "segmentation", None)
-    train_loader = pkg.data.DeviceLoader(Epochs(xtr, ytr, True), tfs["train"], segmenter=seg)
-    test_loader = pkg.data.DeviceLoader(Epochs(xte, yte, False), tfs["test"], segmenter=seg)
+    if train_src is None:
+        train_src, test_src = Epochs(xtr, ytr, True), Epochs(xte, yte, False)
+    train_loader = pkg.data.DeviceLoader(train_src, tfs["train"], segmenter=seg)
+    test_loader = pkg.data.DeviceLoader(test_src, tfs["test"], segmenter=seg)
     work = train_loader.compute_stream if seg is not None else torch.cuda.current_stream()
     work.wait_stream(torch.cuda.current_stream())
     run = pkg.models.sppp.TokenBucketed(model) if (a.bucket_tokens and seg is not None) else model
