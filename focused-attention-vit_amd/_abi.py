@@ -108,6 +108,10 @@ _SIGS = {
     "favit_slic_connect": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
     "favit_cross_entropy": ([vp, vp, vp, vp, i32, i32, f32, vp], C.c_int),
     "favit_adamw": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp], C.c_int),
+    "favit_cross_entropy_ls": ([vp, vp, vp, vp, i32, i32, f32, f32, vp], C.c_int),
+    "favit_grad_norm_workspace": ([], C.c_int64),
+    "favit_grad_norm": ([i32, vp, vp, f32, f32, vp, vp, vp, i64, vp], C.c_int),
+    "favit_adamw_clip": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, vp], C.c_int),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 // HBM-bound row / elementwise kernels of the encoder path (gfx950):
 // LayerNorm fwd/bwd, row reduction, cast, dropout, patchify, CLS/pos prologue,
-// cross-entropy and AdamW.  All are one-pass, 16-B-per-lane coalesced; LayerNorm keeps
+// cross-entropy (plain / label-smoothed), global gradient norm and AdamW (plain / clipped).  All are one-pass, 16-B-per-lane coalesced; LayerNorm keeps
 // the row in registers (one 64-lane wave per token row, shuffle reductions).
 #include "common.h"
 
@@ -564,10 +564,15 @@ __global__ __launch_bounds__(256) void embed_prologue_bwd_chunk_kernel(const flo
 }
 
 // mean cross-entropy rows: loss_rows[b] = lse - logit[label]; dlogits = (softmax - onehot) * grad_scale
+// LS (label smoothing eps, nn.CrossEntropyLoss(label_smoothing=eps)): the target distribution is (1 - eps) * onehot +
+// eps / C, i.e. loss_rows[b] = lse - (1 - eps) * logit[label] - eps * mean_c(logit) and
+// dlogits = (softmax - (1 - eps) * onehot - eps / C) * grad_scale; one more wave reduction (the row sum) per row.
+template <bool LS>
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits,
                                                             const int64_t* __restrict__ labels,
                                                             float* __restrict__ loss_rows, float* __restrict__ dlogits,
-                                                            int B, int C, float grad_scale, unsigned* __restrict__ health) {
+                                                            int B, int C, float grad_scale, float ls_eps,
+                                                            unsigned* __restrict__ health) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
   if (row >= B) return;
@@ -579,38 +584,76 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
   for (int c = lane; c < C; c += 64) s += __expf(lr[c] - m);
   s = wave_sum(s);
   const float lse = m + __logf(s);
+  float xmean = 0.f;
+  if constexpr (LS) {
+    float t = 0.f;
+    for (int c = lane; c < C; c += 64) t += lr[c];
+    xmean = wave_sum(t) / (float)C;
+  }
   const int64_t lab64 = labels[row];
   const bool lab_ok = lab64 >= 0 && lab64 < C;       // out of range (e.g. ignore_index): NaN row, never an OOB read
   const int lab = lab_ok ? (int)lab64 : -1;
   if (lane == 0) {
-    const float lrow = lab_ok ? lse - lr[lab] : __builtin_nanf("");
+    float lrow = __builtin_nanf("");
+    if (lab_ok) {
+      if constexpr (LS) lrow = lse - (1.0f - ls_eps) * lr[lab] - ls_eps * xmean;
+      else lrow = lse - lr[lab];
+    }
     loss_rows[row] = lrow;
     // health word (favit_set_health_word): a non-finite loss row of an in-range label = non-finite logits
     if (health && lab_ok && !isfinite(lrow) && !(atomicOr(health, 1u) & 1u)) health[1] = health[3] + 1;
   }
   if (dlogits) {
     const float inv = 1.0f / s;
-    for (int c = lane; c < C; c += 64)
-      dlogits[(long)row * C + c] = (__expf(lr[c] - m) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+    if constexpr (LS) {
+      const float hot = 1.0f - ls_eps, uni = ls_eps / (float)C;
+      for (int c = lane; c < C; c += 64)
+        dlogits[(long)row * C + c] = (__expf(lr[c] - m) * inv - (c == lab ? hot : 0.f) - uni) * grad_scale;
+    } else {
+      for (int c = lane; c < C; c += 64)
+        dlogits[(long)row * C + c] = (__expf(lr[c] - m) * inv - (c == lab ? 1.f : 0.f)) * grad_scale;
+    }
   }
 }
 
-// torch.optim.AdamW semantics (decoupled weight decay), one flat fp32 chunk
+// torch.optim.AdamW semantics (decoupled weight decay), one flat fp32 chunk.
+// CLIP (favit_adamw_clip): the gradient is also multiplied by the DEVICE scalar *coef (favit_grad_norm's clip
+// coefficient, read when the kernel executes: no host sync between the norm and the update).  With `skip` set and a
+// non-finite coefficient -- the norm pass met a non-finite gradient -- the launch writes nothing but the health word.
+template <bool CLIP>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, bf16_t* __restrict__ p_lp, long n, float lr, float b1, float b2,
-                             float eps, float wd, float bc1, float bc2, float gscale, unsigned* __restrict__ health) {
-  const float step = lr / bc1, rbc2 = rsqrtf(bc2);
+                             float eps, float wd, float bc1, float bc2, float gscale, unsigned* __restrict__ health,
+                             const float* __restrict__ coef, int skip) {
+  float cf = 1.0f;
+  if constexpr (CLIP) {
+    cf = *coef;
+    if (skip && !isfinite(cf)) {           // uniform over the grid: every thread reads the same word
+      if (health && blockIdx.x == 0 && threadIdx.x == 0) {
+        if (!(atomicOr(health, 2u) & 6u)) health[2] = health[3] + 1;
+        atomicAdd(health + 3, 1u);
+      }
+      return;
+    }
+  }
+  // The fused multiply-adds are spelled out (and contraction is off) so that both instantiations round alike,
+  // whatever the compiler would pick for either: coef = 1 must give favit_adamw's bits.  They are the ones the
+  // plain kernel has always compiled to.
   bool bad_g = false, bad_p = false;
+  {
+#pragma clang fp contract(off)
+  const float step = lr / bc1, rbc2 = rsqrtf(bc2), decay = __builtin_fmaf(-lr, wd, 1.0f);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
+    float gi = g[i] * gscale;
+    if constexpr (CLIP) gi *= cf;
+    const float mi = __builtin_fmaf(1.0f - b1, gi, b1 * m[i]);
+    const float vi = __builtin_fmaf(gi, (1.0f - b2) * gi, b2 * v[i]);
+    const float pi = __builtin_fmaf(decay, p[i], -((step * mi) / __builtin_fmaf(rbc2, sqrtf(vi), eps)));
     p[i] = pi; m[i] = mi; v[i] = vi;
     if (p_lp) p_lp[i] = (bf16_t)pi;
     bad_g |= !isfinite(gi);
     bad_p |= !isfinite(pi);
+  }
   }
   // Health word (favit_set_health_word; null = off): the update reads every gradient and writes every parameter
   // anyway, so noticing the first non-finite one costs two compares per element and no memory traffic.  [0] flags
@@ -621,6 +664,89 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     if (f && !(atomicOr(health, f) & 6u)) health[2] = health[3] + 1;
     __syncthreads();
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(health + 3, 1u);   // (stream order: one AdamW launch at a time)
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Global L2 norm of up to GRAD_NORM_MAX flat fp32 buffers (the optimizer's gradient buffers) and the clip
+// coefficient of torch.nn.utils.clip_grad_norm_, on the device and bitwise reproducible.
+// Launch 1: GRAD_NORM_PARTS workgroups of 256 threads, whatever the data.  Thread t of the grid walks, buffer by
+// buffer, the 16-byte vectors t, t + T, t + 2T, ... of the buffer's aligned body (T = threads of the grid) and one
+// element of its unaligned head / tail, and adds the exact double-precision squares to a private double sum; the
+// workgroup folds its 256 sums (shuffles inside a wave, then waves 0..3 in that order) and stores ONE double into
+// its own workspace slot -- also when it owned no element, the workspace arrives uninitialised.  Which thread adds
+// which element in which order depends only on the buffers' addresses and lengths: no atomics, the same bits every
+// run.  Launch 2: one workgroup adds the GRAD_NORM_PARTS partials in a fixed order and writes the two results.
+// ---------------------------------------------------------------------------------
+constexpr int GRAD_NORM_MAX = 16;
+constexpr int GRAD_NORM_PARTS = 1024;
+struct GradNormBufs {
+  const float* p[GRAD_NORM_MAX];
+  long n[GRAD_NORM_MAX];
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over the workgroup's 256 threads; the result is valid in thread 0
+__device__ __forceinline__ double block256_sum_f64(double v) {
+  __shared__ double red[4];
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ void sq_acc(double& a0, double& a1, const float4 x) {
+  a0 = fma((double)x.x, (double)x.x, a0);
+  a1 = fma((double)x.y, (double)x.y, a1);
+  a0 = fma((double)x.z, (double)x.z, a0);
+  a1 = fma((double)x.w, (double)x.w, a1);
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(GradNormBufs gb, int nbuf, double* __restrict__ part) {
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, T = (long)gridDim.x * 256;
+  double a0 = 0.0, a1 = 0.0;
+  for (int b = 0; b < nbuf; ++b) {
+    const float* __restrict__ p = gb.p[b];
+    const long n = gb.n[b];
+    // p + head is 16-byte aligned (p is 4-byte aligned): head in 0..3 elements, then n4 vectors, then tail in 0..3
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    const long tail0 = head + (n4 << 2);
+    const float4* __restrict__ body = reinterpret_cast<const float4*>(p + head);
+    long i = tid;
+    for (; i + 3 * T < n4; i += 4 * T) {             // four independent 16-byte loads in flight
+      const float4 x0 = body[i], x1 = body[i + T], x2 = body[i + 2 * T], x3 = body[i + 3 * T];
+      sq_acc(a0, a1, x0); sq_acc(a0, a1, x1); sq_acc(a0, a1, x2); sq_acc(a0, a1, x3);
+    }
+    for (; i < n4; i += T) sq_acc(a0, a1, body[i]);
+    if (tid < head) a0 = fma((double)p[tid], (double)p[tid], a0);
+    if (tid < n - tail0) a0 = fma((double)p[tail0 + tid], (double)p[tail0 + tid], a0);
+  }
+  const double s = block256_sum_f64(a0 + a1);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ part, float scale, float max_norm,
+                                                              float* __restrict__ out, unsigned* __restrict__ skipped) {
+  double a = 0.0;
+#pragma unroll
+  for (int k = 0; k < GRAD_NORM_PARTS / 256; ++k) a += part[threadIdx.x + 256 * k];
+  const double s = block256_sum_f64(a);
+  if (threadIdx.x == 0) {
+    const float norm = (float)((double)scale * sqrt(s));
+    float cf = 1.0f;
+    if (!isfinite(norm)) {
+      cf = __builtin_nanf("");
+      if (skipped) *skipped += 1u;                     // (stream order: one finalize at a time)
+    } else if (max_norm > 0.f) {
+      cf = fminf(1.0f, __fdiv_rn(max_norm, norm + 1e-6f));
+    }
+    out[0] = norm;
+    out[1] = cf;
   }
 }
 
@@ -1014,7 +1140,18 @@ extern "C" int favit_embed_prologue_bwd(const float* dx, void* dtok, int dtok_dt
 extern "C" int favit_cross_entropy(const float* logits, const int64_t* labels, float* loss_rows, float* dlogits,
                                    int32_t B, int32_t C, float grad_scale, void* stream) {
   if (!logits || !labels || !loss_rows || B <= 0 || C <= 0) return FAVIT_ERR_INVALID;
-  hipLaunchKernelGGL(cross_entropy_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), logits, labels, loss_rows, dlogits, B, C, grad_scale, favit_health_ptr_());
+  hipLaunchKernelGGL(cross_entropy_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), logits, labels, loss_rows, dlogits, B, C, grad_scale, 0.0f, favit_health_ptr_());
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_cross_entropy_ls(const float* logits, const int64_t* labels, float* loss_rows, float* dlogits,
+                                      int32_t B, int32_t C, float grad_scale, float label_smoothing, void* stream) {
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return FAVIT_ERR_INVALID;
+  // eps = 0 is the unsmoothed loss itself (as in torch, which skips the smoothing term then): same kernel, same bits
+  if (label_smoothing == 0.f) return favit_cross_entropy(logits, labels, loss_rows, dlogits, B, C, grad_scale, stream);
+  if (!logits || !labels || !loss_rows || B <= 0 || C <= 0) return FAVIT_ERR_INVALID;
+  hipLaunchKernelGGL(cross_entropy_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), logits, labels, loss_rows, dlogits, B, C, grad_scale, label_smoothing, favit_health_ptr_());
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }
@@ -1024,7 +1161,49 @@ extern "C" int favit_adamw(float* p, const float* g, float* m, float* v, void* p
                            float grad_scale, void* stream) {
   if (!p || !g || !m || !v || n < 0) return FAVIT_ERR_INVALID;
   if (n == 0) return FAVIT_OK;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_());
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), (const float*)nullptr, 0);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_adamw_clip(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                                float beta1, float beta2, float eps, float weight_decay, float bias_c1, float bias_c2,
+                                float grad_scale, const float* coef, int32_t skip_nonfinite, void* stream) {
+  if (n < 0 || !coef) return FAVIT_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(coef) & 3) return FAVIT_ERR_ALIGN;
+  if (n == 0) return FAVIT_OK;                       // (an empty group: nothing to read, whatever its pointers)
+  if (!p || !g || !m || !v) return FAVIT_ERR_INVALID;
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), coef, (int)(skip_nonfinite != 0));
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int64_t favit_grad_norm_workspace(void) { return (int64_t)GRAD_NORM_PARTS * (int64_t)sizeof(double); }
+
+extern "C" int favit_grad_norm(int32_t n, const float* const* bufs, const int64_t* lens, float scale, float max_norm,
+                               float* out, uint32_t* skipped, void* ws, int64_t ws_bytes, void* stream) {
+  if (n < 0 || n > GRAD_NORM_MAX || (n > 0 && (!bufs || !lens)) || !out || !ws || !(max_norm == max_norm))
+    return FAVIT_ERR_INVALID;
+  if (ws_bytes < favit_grad_norm_workspace()) return FAVIT_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || (reinterpret_cast<uintptr_t>(out) & 3) ||
+      (reinterpret_cast<uintptr_t>(skipped) & 3))
+    return FAVIT_ERR_ALIGN;
+  GradNormBufs gb;
+  for (int i = 0; i < GRAD_NORM_MAX; ++i) {
+    gb.p[i] = nullptr;
+    gb.n[i] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (lens[i] < 0 || (lens[i] > 0 && !bufs[i])) return FAVIT_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(bufs[i]) & 3) return FAVIT_ERR_ALIGN;
+    gb.p[i] = bufs[i];
+    gb.n[i] = (long)lens[i];
+  }
+  hipStream_t st = as_stream(stream);
+  double* part = reinterpret_cast<double*>(ws);
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(GRAD_NORM_PARTS), dim3(256), 0, st, gb, (int)n, part);
+  FAVIT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, st, (const double*)part, scale, max_norm, out, skipped);
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }

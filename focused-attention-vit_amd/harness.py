@@ -105,11 +105,18 @@ def evaluate(model, loader: Iterable, batch_size: Optional[int] = None) -> Dict[
 
 
 def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer, epochs: int,
-        log: Callable[[str], None] = print) -> Dict[str, object]:
+        log: Callable[[str], None] = print, label_smoothing: float = 0.0, schedule=None) -> Dict[str, object]:
     """The reference's epoch loop (experiments/mhla_pretrained.py:350-420) with device-side statistics: one host
-    sync per EPOCH.  optimizer: train.FusedAdamW (hot path) or any torch.optim optimizer."""
+    sync per EPOCH.  optimizer: train.FusedAdamW (hot path) or any torch.optim optimizer.
+    label_smoothing: the TRAINING loss is nn.CrossEntropyLoss(label_smoothing=...)'s; evaluation keeps the plain one.
+    schedule: an object with step() (train.WarmupCosine), called after every optimizer step.
+    history["grad_norm"] (the epoch mean of the pre-clip global gradient norm, summed on the device) is present
+    when the optimizer exposes `grad_norm` (train.FusedAdamW with max_grad_norm or skip_nonfinite)."""
     dev = next(model.parameters()).device
     hist: Dict[str, List[float]] = {"train_loss": [], "train_acc": [], "val_loss": [], "val_acc": [], "epoch_time": []}
+    track_norm = getattr(optimizer, "grad_norm", None) is not None
+    if track_norm:
+        hist["grad_norm"] = []
     t_start = time.perf_counter()
     peak_mb = 0.0
     for ep in range(epochs):
@@ -119,18 +126,25 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         loss_sum = torch.zeros((), device=dev)
         correct = torch.zeros((), device=dev, dtype=torch.int64)
         total = n_batches = 0
+        norm_sum = torch.zeros((), device=dev) if track_norm else None
         for images, labels in train_loader:
             optimizer.zero_grad()
             out = model(images)
-            loss = T.cross_entropy(out, labels)
+            loss = T.cross_entropy(out, labels, label_smoothing)
             loss.backward()
             optimizer.step()
+            if schedule is not None:
+                schedule.step()
+            if track_norm:
+                norm_sum += optimizer.grad_norm
             loss_sum += loss.detach()
             correct += (out.detach().argmax(1) == labels).sum()
             total += labels.numel()
             n_batches += 1
         hist["train_loss"].append(loss_sum.item() / max(1, n_batches))          # the epoch's single sync
         hist["train_acc"].append(100.0 * correct.item() / max(1, total))
+        if track_norm:
+            hist["grad_norm"].append(norm_sum.item() / max(1, n_batches))
         if val_loader is not None:
             ev = evaluate(model, val_loader)
             hist["val_loss"].append(ev["test_loss"])

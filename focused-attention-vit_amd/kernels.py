@@ -785,8 +785,11 @@ def slic_stage_times(images, n_segments=16, compactness=0.1, sigma=1.0, max_num_
     return out
 
 
-def cross_entropy(logits, labels, grad_scale=None):
-    """Returns (loss_rows[B], dlogits or None)."""
+def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0):
+    """Returns (loss_rows[B], dlogits or None).  label_smoothing = eps in [0, 1): the loss of
+    nn.CrossEntropyLoss(label_smoothing=eps) (favit_cross_entropy_ls); 0 calls favit_cross_entropy."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
     require_gpu(logits, labels)
     if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise TypeError("cross_entropy: logits must be a contiguous fp32 [B, C] tensor")
@@ -796,13 +799,69 @@ def cross_entropy(logits, labels, grad_scale=None):
                         "(out-of-range labels, e.g. ignore_index = -100, give a NaN loss row)")
     loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
     dlog = torch.empty_like(logits) if grad_scale is not None else None
-    _abi.check(_abi.lib().favit_cross_entropy(_p(logits), _p(labels), _p(loss_rows), _p(dlog), B, Cn,
-                                              0.0 if grad_scale is None else grad_scale, _st()), "favit_cross_entropy")
+    gs = 0.0 if grad_scale is None else grad_scale
+    if label_smoothing:
+        _abi.check(_abi.lib().favit_cross_entropy_ls(_p(logits), _p(labels), _p(loss_rows), _p(dlog), B, Cn, gs,
+                                                     float(label_smoothing), _st()), "favit_cross_entropy_ls")
+    else:
+        _abi.check(_abi.lib().favit_cross_entropy(_p(logits), _p(labels), _p(loss_rows), _p(dlog), B, Cn, gs, _st()),
+                   "favit_cross_entropy")
     return loss_rows, dlog
 
 
-def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None):
+GRAD_NORM_MAX_BUFS = 16
+
+
+def grad_norm_workspace(device) -> torch.Tensor:
+    """An (uninitialised) workspace for grad_norm; allocate once and pass it as `ws`."""
+    return torch.empty(int(_abi.lib().favit_grad_norm_workspace()) // 8, dtype=torch.float64, device=device)
+
+
+def grad_norm(bufs, scale=1.0, max_norm=0.0, out=None, skipped=None, ws=None):
+    """Global L2 norm of up to 16 flat fp32 tensors (any 4-byte-aligned start, any length) on the device, bitwise
+    reproducible (favit_grad_norm).  Returns `out`, two fp32: out[0] = scale * norm, out[1] = the coefficient of
+    torch.nn.utils.clip_grad_norm_, min(1, max_norm / (out[0] + 1e-6)) -- 1 without max_norm, NaN when out[0] is not
+    finite, in which case `skipped` (one int32 on the device, optional) is incremented.  No host sync."""
+    bufs = list(bufs)
+    n = len(bufs)
+    if n > GRAD_NORM_MAX_BUFS:
+        raise ValueError(f"grad_norm: at most {GRAD_NORM_MAX_BUFS} buffers per call, got {n}")
+    if not n and out is None:
+        raise ValueError("grad_norm: no buffer and no `out` to take the device from")
+    require_gpu(*bufs, out, skipped, ws)
+    for t in bufs:
+        if t.dtype != torch.float32 or (t.numel() and not t.is_contiguous()):
+            raise TypeError("grad_norm: every buffer must be a contiguous fp32 tensor")
+    dev = bufs[0].device if n else out.device
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != 2 or not out.is_contiguous():
+        raise TypeError("grad_norm: out must be two contiguous fp32")
+    if skipped is not None and (skipped.dtype != torch.int32 or skipped.numel() != 1):
+        raise TypeError("grad_norm: skipped must be one int32")
+    if ws is None:
+        ws = grad_norm_workspace(dev)
+    ptrs = (C.c_void_p * max(1, n))(*[t.data_ptr() if t.numel() else None for t in bufs])
+    lens = (C.c_int64 * max(1, n))(*[t.numel() for t in bufs])
+    _abi.check(_abi.lib().favit_grad_norm(n, ptrs, lens, float(scale), float(max_norm), _p(out), _p(skipped), _p(ws),
+                                          ws.numel() * ws.element_size(), _st()), "favit_grad_norm")
+    return out
+
+
+def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None, coef=None, skip_nonfinite=False):
+    """coef: one fp32 on the DEVICE (grad_norm's out[1:2]) the gradient is multiplied by when the kernel runs
+    (favit_adamw_clip); with skip_nonfinite a non-finite coefficient leaves p, m, v and p_lp untouched."""
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    _abi.check(_abi.lib().favit_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_lp), p.numel(), lr, beta1, beta2, eps, wd, bc1,
-                                      bc2, grad_scale, _st()), "favit_adamw")
+    if coef is None:
+        if skip_nonfinite:
+            raise ValueError("adamw: skip_nonfinite needs the device coefficient of grad_norm (coef)")
+        _abi.check(_abi.lib().favit_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_lp), p.numel(), lr, beta1, beta2, eps, wd,
+                                          bc1, bc2, grad_scale, _st()), "favit_adamw")
+        return
+    require_gpu(coef)
+    if coef.dtype != torch.float32 or coef.numel() != 1:
+        raise TypeError("adamw: coef must be one fp32 on the device")
+    _abi.check(_abi.lib().favit_adamw_clip(_p(p), _p(g), _p(m), _p(v), _p(p_lp), p.numel(), lr, beta1, beta2, eps, wd,
+                                           bc1, bc2, grad_scale, _p(coef), int(bool(skip_nonfinite)), _st()),
+               "favit_adamw_clip")

@@ -19,20 +19,22 @@ class _CrossEntropyFn(torch.autograd.Function):
     """nn.CrossEntropyLoss() (mean reduction) forward + gradient in one kernel."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, label_smoothing=0.0):
         B = logits.shape[0]
-        rows, dlog = K.cross_entropy(logits.contiguous(), labels.contiguous(), grad_scale=1.0 / B)
+        rows, dlog = K.cross_entropy(logits.contiguous(), labels.contiguous(), grad_scale=1.0 / B,
+                                     label_smoothing=label_smoothing)
         ctx.save_for_backward(dlog)
         return K.reduce_rows(rows.view(B, 1))[0] / B
 
     @staticmethod
     def backward(ctx, g):
         (dlog,) = ctx.saved_tensors
-        return dlog * g, None
+        return dlog * g, None, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    return _CrossEntropyFn.apply(logits, labels)
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
+    """nn.CrossEntropyLoss(label_smoothing=label_smoothing)(logits, labels), mean reduction."""
+    return _CrossEntropyFn.apply(logits, labels, float(label_smoothing))
 
 
 def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = None,
@@ -60,14 +62,34 @@ def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = N
 class FusedAdamW:
     """torch.optim.AdamW semantics; one favit_adamw launch per parameter group over flat
     parameter / gradient / moment buffers (and the DP all-reduce runs on the same flat
-    gradient buffers, see dp.py)."""
+    gradient buffers, see dp.py).
+
+    max_grad_norm: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) in front of every update, on the device:
+    step() computes the global norm of all groups' (all-reduced) gradients once (favit_grad_norm, scale = 1 / world)
+    and every group's AdamW launch multiplies its gradients by the coefficient it reads from device memory
+    (favit_adamw_clip) -- no host sync, no extra pass over the gradients.
+    skip_nonfinite: an update whose gradient norm is inf / NaN is not applied: p, m, v and the bf16 mirror keep their
+    values and `skipped_steps` counts it.  Works without max_grad_norm (the coefficient is then 1 or "skip").  The
+    host-side step count behind the bias correction still advances on a skipped step (the host never learns of the
+    skip): the next applied update uses bias-correction factors one step further on, which after the first few
+    steps is a difference far below the update's own rounding.
+    Read-outs (None when both options are off): `grad_norm`, a 0-dim fp32 device view of the last step's pre-clip
+    norm, and `skipped_steps`, a 0-dim int32 device view.  Both options need at most 16 parameter groups."""
 
     def __init__(self, groups, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, bucket_mb=None,
-                 distributed=None, wire_dtype=None):
+                 distributed=None, wire_dtype=None, max_grad_norm=None, skip_nonfinite=False):
         if isinstance(groups, torch.nn.Module):
             groups = [{"params": list(groups.parameters())}]
         elif groups and not isinstance(groups[0], dict):
             groups = [{"params": list(groups)}]
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FusedAdamW: max_grad_norm must be > 0 (or None for no clipping), got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard = self.max_grad_norm is not None or self.skip_nonfinite
+        if self._guard and len(groups) > K.GRAD_NORM_MAX_BUFS:
+            raise ValueError(f"FusedAdamW: max_grad_norm / skip_nonfinite take at most {K.GRAD_NORM_MAX_BUFS} parameter "
+                             f"groups, got {len(groups)}")
         self.groups = []
         dist_on = torch.distributed.is_initialized() if distributed is None else distributed
         for g in groups:
@@ -85,6 +107,18 @@ class FusedAdamW:
                 self.groups[-1]["mirror"] = F.register_lp_mirror(flat.flat_p, self.groups[-1]["lp"], flat.params)
         self.steps = 0
         self.world = torch.distributed.get_world_size() if dist_on else 1
+        # norm / coefficient, skip counter and the norm kernel's workspace live as long as the optimizer: step()
+        # allocates nothing (and a GraphedStep built on it keeps replaying against the same addresses)
+        self.grad_norm = self.skipped_steps = None
+        if self._guard:
+            dev = self.groups[0]["flat"].flat_p.device if self.groups else torch.device("cuda", torch.cuda.current_device())
+            if dev.type != "cuda":
+                raise RuntimeError("FusedAdamW: max_grad_norm / skip_nonfinite run in HIP kernels; the parameters are "
+                                   "on the CPU (there is no CPU fallback)")
+            self._norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._norm_ws = K.grad_norm_workspace(dev)
+            self.grad_norm, self.skipped_steps = self._norm_out[0], self._skipped[0]
         syncs = [g["sync"] for g in self.groups if g["sync"] is not None]
         if syncs:
             F.set_grad_ready_hook(lambda p: [s.grad_ready(p) for s in syncs])
@@ -120,6 +154,21 @@ class FusedAdamW:
 
     def step(self):
         self.steps += 1
+        if self._guard:
+            for g in self.groups:                      # the norm is that of the COMPLETE all-reduced gradient
+                if g["sync"] is not None:
+                    g["sync"].finish(average=False)
+            K.grad_norm([g["flat"].flat_g for g in self.groups], scale=1.0 / self.world,
+                        max_norm=self.max_grad_norm or 0.0, out=self._norm_out, skipped=self._skipped, ws=self._norm_ws)
+            coef = self._norm_out[1:2]
+            for g in self.groups:
+                f = g["flat"]
+                K.adamw(f.flat_p, f.flat_g, g["m"], g["v"], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                        g["weight_decay"], self.steps, grad_scale=1.0 / self.world, p_lp=g["lp"], coef=coef,
+                        skip_nonfinite=self.skip_nonfinite)
+            # (a skipped launch left parameters and mirrors as they were: still a matching pair)
+            F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
+            return
         for g in self.groups:
             if g["sync"] is not None:
                 g["sync"].finish(average=False)
@@ -128,6 +177,51 @@ class FusedAdamW:
                     g["weight_decay"], self.steps, grad_scale=1.0 / self.world, p_lp=g["lp"])
         # the AdamW kernel rewrote the bf16 mirrors itself: they stay valid across the epoch bump
         F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
+
+
+class WarmupCosine:
+    """Learning-rate schedule on the host: linear warm-up, then half a cosine down to min_ratio.
+
+    factor(t), for the optimizer step with index t = 0, 1, ...:
+        t <  warmup_steps:  (t + 1) / warmup_steps                       (reaches 1 on the last warm-up step)
+        t >= warmup_steps:  min_ratio + (1 - min_ratio) * (1 + cos(pi * x)) / 2,
+                            x = min(1, (t - warmup_steps) / max(1, total_steps - warmup_steps))
+    Every group's lr is its value at construction times factor(t), so the ratios between groups (param_groups:
+    latent_proj at 5x, the head's own rate) are preserved.  The constructor sets the rates of step 0; call step()
+    after every optimizer step.  The learning rate is a by-value argument of the eager AdamW launch, so no kernel is
+    involved and a GraphedStep picks the new value up at its next call."""
+
+    def __init__(self, opt, warmup_steps: int, total_steps: int, min_ratio: float = 0.0):
+        if warmup_steps < 0 or total_steps <= 0 or warmup_steps > total_steps:
+            raise ValueError(f"WarmupCosine: need 0 <= warmup_steps <= total_steps and total_steps > 0, got "
+                             f"{warmup_steps}, {total_steps}")
+        if not 0.0 <= min_ratio <= 1.0:
+            raise ValueError(f"WarmupCosine: min_ratio must be in [0, 1], got {min_ratio}")
+        self.opt, self.warmup_steps, self.total_steps, self.min_ratio = opt, int(warmup_steps), int(total_steps), float(min_ratio)
+        self._groups = opt.groups if hasattr(opt, "groups") else opt.param_groups
+        self.base_lrs = [g["lr"] for g in self._groups]
+        self.t = 0
+        self._apply()
+
+    def factor(self, t: int) -> float:
+        import math
+        if t < self.warmup_steps:
+            return (t + 1) / self.warmup_steps
+        x = min(1.0, (t - self.warmup_steps) / max(1, self.total_steps - self.warmup_steps))
+        return self.min_ratio + (1.0 - self.min_ratio) * 0.5 * (1.0 + math.cos(math.pi * x))
+
+    def _apply(self):
+        f = self.factor(self.t)
+        for g, base in zip(self._groups, self.base_lrs):
+            g["lr"] = base * f
+
+    def step(self):
+        self.t += 1
+        self._apply()
+
+    @property
+    def last_lr(self):
+        return [g["lr"] for g in self._groups]
 
 
 class Health:
@@ -182,11 +276,11 @@ class Health:
         return out or None
 
 
-def train_step(model, images, labels, opt: FusedAdamW):
+def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0):
     """One step of the reference's hot loop; returns the (device) loss tensor, no host sync."""
     opt.zero_grad()
     logits = model(images)
-    loss = cross_entropy(logits, labels)
+    loss = cross_entropy(logits, labels, label_smoothing)
     loss.backward()
     opt.step()
     return loss
@@ -213,7 +307,8 @@ class GraphedStep:
     and for SPPP models ``model.assume_num_tokens`` set (the per-forward token-count check is a host sync)."""
 
     def __init__(self, model: torch.nn.Module, opt: FusedAdamW, images: torch.Tensor, labels: torch.Tensor,
-                 warmup: int = 3, segments: Optional[int] = None, static_inputs: bool = False):
+                 warmup: int = 3, segments: Optional[int] = None, static_inputs: bool = False,
+                 label_smoothing: float = 0.0):
         """static_inputs: `images` / `labels` themselves are the buffers the captured kernels read (no clone at capture,
         no copy per call when the step is called with these same tensors): for a producer that writes every batch into
         fixed device buffers (bench.py's resident synthetic batch).  Default: private copies, one device-to-device copy
@@ -221,6 +316,7 @@ class GraphedStep:
         if K.GEMM_TRACE is not None:
             raise RuntimeError("GraphedStep: disable kernels.GEMM_TRACE (event records cannot be captured)")
         self.model, self.opt = model, opt
+        self.label_smoothing = float(label_smoothing)          # (a by-value kernel argument: frozen into the graph)
         self.x, self.y = (images, labels) if static_inputs else (images.clone(), labels.clone())
         syncs = [g["sync"] for g in opt.groups if g["sync"] is not None and g["sync"]._active]
         self._syncs = syncs
@@ -288,7 +384,7 @@ class GraphedStep:
                 self.epoch.add_(1)
             self.opt.zero_grad()
             with F.encoder_segments(self.segments) as seg:
-                loss = cross_entropy(self.model(self.x), self.y)
+                loss = cross_entropy(self.model(self.x), self.y, self.label_smoothing)
             bounds = list(seg.boundaries)
         if graphs is not None:
             self.loss = loss

@@ -456,6 +456,39 @@ int favit_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, int6
                 float beta2, float eps, float weight_decay, float bias_c1, float bias_c2, float grad_scale,
                 void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Stabilisers of the training step (additive in ABI 8): label smoothing, global-norm gradient clipping and
+ * skipping a non-finite update, all without a host sync.
+ * ---------------------------------------------------------------------------------- */
+/* favit_cross_entropy with nn.CrossEntropyLoss(label_smoothing = eps), 0 <= eps < 1 (else FAVIT_ERR_INVALID):
+ *   loss_rows[b] = lse - (1 - eps) * x[label] - eps * mean_c(x)
+ *   dlogits      = (softmax - (1 - eps) * onehot - eps / C) * grad_scale
+ * eps = 0 runs favit_cross_entropy itself (bit-identical).  Out-of-range labels and the health word as there. */
+int favit_cross_entropy_ls(const float* logits, const int64_t* labels, float* loss_rows, float* dlogits, int32_t B,
+                           int32_t C, float grad_scale, float label_smoothing, void* stream);
+
+/* Global L2 norm of n (0..16) flat fp32 buffers, bufs[i] / lens[i] (host arrays, copied by value into the launch):
+ * any 4-byte-aligned address, any length >= 0 (a NULL buffer needs length 0).
+ *   out[0] = scale * sqrt(sum_i sum_j bufs[i][j]^2)      (scale: AdamW's grad_scale, 1 / world)
+ *   out[1] = max_norm > 0 ? min(1, max_norm / (out[0] + 1e-6f)) : 1      (torch.nn.utils.clip_grad_norm_)
+ * If out[0] is not finite, out[1] = NaN and, with skipped != NULL, *skipped (device uint32) is incremented.
+ * Squares and sums are double precision; out[0] is within 1e-6 relative of a float64 evaluation (its own fp32
+ * rounding and that of `scale` are the only ones).  Two launches: a fixed grid whose workgroups each store one
+ * partial into `ws`, and one workgroup that adds the partials in a fixed order.  No atomics: the same inputs at the
+ * same addresses give the same bits in every run.  ws: device workspace of ws_bytes >= favit_grad_norm_workspace()
+ * bytes, 8-byte aligned, contents irrelevant on entry. */
+int64_t favit_grad_norm_workspace(void);
+int favit_grad_norm(int32_t n, const float* const* bufs, const int64_t* lens, float scale, float max_norm,
+                    float* out, uint32_t* skipped, void* ws, int64_t ws_bytes, void* stream);
+
+/* favit_adamw with the gradient (g[i] * grad_scale) * coef[0]; coef is a DEVICE scalar (favit_grad_norm's out + 1)
+ * read when the kernel executes.  coef[0] == 1.0f is bit-identical to favit_adamw.  skip_nonfinite != 0 and a
+ * non-finite coef[0]: p, m, v and p_bf16 are left untouched; the launch still counts itself in the health word and
+ * sets its gradient flag.  skip_nonfinite == 0: a NaN coefficient propagates into p, m and v, as in torch. */
+int favit_adamw_clip(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, float bias_c1, float bias_c2, float grad_scale,
+                     const float* coef, int32_t skip_nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,14 @@ def parse_args(argv=None):
     ap.add_argument("--weight_decay", type=float, default=0.05)
     ap.add_argument("--head_learning_rate", type=float, default=1e-3)
     ap.add_argument("--compute_dtype", default="bf16", choices=["bf16", "fp32", "fp8"])
+    ap.add_argument("--clip_grad_norm", type=float, default=None,
+                    help="clip the global gradient norm to this value in front of every update (default: no clipping)")
+    ap.add_argument("--skip_nonfinite", action="store_true",
+                    help="do not apply an update whose gradient norm is inf / NaN (counted, reported at the end)")
+    ap.add_argument("--label_smoothing", type=float, default=0.0, help="training loss only; evaluation keeps plain cross-entropy")
+    ap.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine"],
+                    help="cosine: linear warm-up over --warmup_epochs, then half a cosine to zero over the remaining epochs")
+    ap.add_argument("--warmup_epochs", type=float, default=0.0, help="--lr_schedule cosine: length of the linear warm-up")
     ap.add_argument("--bucket_tokens", action="store_true",
                     help="sppp_mhla: run batches that mix images with num_superpixels and num_superpixels - 1 tokens group by "
                          "group (models.sppp.TokenBucketed; the reference -- and this tool without the flag -- fails on "
@@ -205,7 +213,8 @@ def main(argv=None):
     model = model.cuda()
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
     opt = pkg.train.FusedAdamW(pkg.train.param_groups(model, lr=a.learning_rate, head_lr=a.head_learning_rate),
-                               lr=a.learning_rate, weight_decay=a.weight_decay, distributed=False)
+                               lr=a.learning_rate, weight_decay=a.weight_decay, distributed=False,
+                               max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite)
 
     class Epochs:            # a fresh shuffle per epoch
         def __init__(self, x, y, shuffle):
@@ -224,8 +233,13 @@ def main(argv=None):
     work = train_loader.compute_stream if seg is not None else torch.cuda.current_stream()
     work.wait_stream(torch.cuda.current_stream())
     run = pkg.models.sppp.TokenBucketed(model) if (a.bucket_tokens and seg is not None) else model
+    schedule = None
+    if a.lr_schedule == "cosine":
+        per_epoch = max(1, len(train_src))
+        schedule = pkg.train.WarmupCosine(opt, int(round(a.warmup_epochs * per_epoch)), max(1, a.epochs * per_epoch))
     with torch.cuda.stream(work):
-        res = pkg.harness.fit(run, train_loader, test_loader, opt, a.epochs)
+        res = pkg.harness.fit(run, train_loader, test_loader, opt, a.epochs, label_smoothing=a.label_smoothing,
+                              schedule=schedule)
         ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
     torch.cuda.current_stream().wait_stream(work)
     row = {"model": a.experiment, "img_size": a.img_size, "patch_size": a.patch_size, "embed_dim": a.embed_dim, "depth": a.depth,
@@ -234,6 +248,8 @@ def main(argv=None):
            "final_val_acc": res["final_val_acc"], "final_val_loss": res["final_val_loss"], "test_acc": ev["test_acc"],
            "test_loss": ev["test_loss"], "avg_inference_time_per_image": ev["avg_inference_time_per_image"],
            "peak_gpu_memory_mb": res["peak_gpu_memory_mb"]}
+    if opt.skipped_steps is not None:
+        print(f"updates skipped for a non-finite gradient norm: {int(opt.skipped_steps)}")
     path = os.path.join(a.results_dir, f"exp_{a.experiment}.csv")
     pkg.harness.save_results_csv(path, row)
     print(f"Results saved to {path}")
