@@ -2230,6 +2230,7 @@ extern "C" int favit_mhla_fold_bwd(const float* dweff, const float* dbeff, const
   if (!dweff || !dbeff || !wqkv || !bqkv || !wl || !dwqkv || !dbqkv || !dwl || !dbl || D <= 0 || H <= 0 || D % H)
     return FAVIT_ERR_INVALID;
   const int hd = D / H;
+  if (hd != 16 && hd != 32 && hd != 64) return FAVIT_ERR_UNSUPPORTED;   // before the zero fills: no launch at all
   hipStream_t st = as_stream(stream);
   if (!accumulate) {
     (void)favit_zero_async(dwl, sizeof(float) * hd * hd, st);

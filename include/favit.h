@@ -202,11 +202,14 @@ int favit_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t
  *   models/vit.py:155,157,251; models/vit_mhla.py:45,64,88,107,188,241.
  * x is the fp32 residual stream with row stride ldx (lets the head normalise x[:,0]
  * only); y has dtype y_dtype; mean/rstd [rows] are saved for backward.
- * Backward: dx = LN'(dy) (+ dres if given); optional low-precision copy dx_lp, optionally with the dropout mask
- * (lp_dropout_p, lp_dropout_seed; element index row*D + col, as favit_dropout) of the branch it feeds; the
+ * Backward: dx = LN'(dy) (+ dres if given); dres is read with the SAME row stride as dx is written with (lddx), so
+ * a strided dx takes an equally strided dres; optional low-precision copy dx_lp ([rows, D] contiguous, the
+ * dtype of dy), optionally with the dropout mask (lp_dropout_p, lp_dropout_seed; element index row*D + col, as
+ * favit_dropout) of the branch it feeds; dx itself is never masked; the
  * affine gradients are produced as `nparts` partial sums in a [2][nparts][D] workspace
- * (dbeta_part = dgamma_part + nparts*D) and folded deterministically (no atomics) into dgamma[D]
- * and dbeta[D] (accumulate=1 adds to them); dgamma = NULL skips the fold.
+ * (dbeta_part = dgamma_part + nparts*D) and folded into dgamma[D] and dbeta[D]: deterministically (no atomics)
+ * with accumulate=0, ADDED to them with the rows split eight ways and fp32 atomics with accumulate=1;
+ * dgamma = NULL skips the fold (the caller folds the workspace later, favit_reduce_rows_multi, or not at all).
  * ---------------------------------------------------------------------------------- */
 int favit_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y, int y_dtype,
                         float* mean, float* rstd, int64_t rows, int32_t D, float eps, void* stream);
