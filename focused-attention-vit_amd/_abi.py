@@ -93,6 +93,8 @@ _SIGS = {
     "favit_patchify_bwd": ([vp, vp, i32, i32, i32, i32, vp], C.c_int),
     "favit_embed_prologue_fwd": ([vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_embed_prologue_bwd": ([vp, vp, C.c_int, vp, vp, i32, i32, i32, vp], C.c_int),
+    "favit_rows_cut_fwd": ([vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
+    "favit_rows_cut_bwd": ([vp, vp, vp, C.c_int, i32, i32, i32, i32, i32, vp], C.c_int),
     "favit_dropout": ([vp, vp, C.c_int, i64, f32, u64, vp], C.c_int),
     "favit_sppp_map_patches": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_sppp_pool_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),

@@ -563,6 +563,59 @@ __global__ __launch_bounds__(256) void embed_prologue_bwd_chunk_kernel(const flo
   }
 }
 
+// Row cut of the residual stream (CLS-only encoders): every image keeps its first `a` and its last
+// `b` rows, stored one after the other.  VW = floats per access (4 when D % 4 == 0 and the bases are 16-byte aligned).
+// Grid: x walks the (row, column vector) pairs of one image with 32-bit index math, y the images.
+// fwd: y[B, a + b, D] = rows [0, a) and [n_in - b, n_in) of x[B, n_in, D].
+template <int VW>
+__global__ __launch_bounds__(256) void rows_cut_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B,
+                                                           int n_in, int a, int b, int D) {
+  const unsigned dvn = D / VW, n_out = a + b;
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= n_out * dvn) return;
+  const unsigned l = idx / dvn, dv = idx - l * dvn;
+  const unsigned ls = l < (unsigned)a ? l : l + (n_in - n_out);
+  for (int img = blockIdx.y; img < B; img += gridDim.y) {
+    const float* s = x + ((long)img * n_in + ls) * D + dv * VW;
+    float* o = y + ((long)img * n_out + l) * D + dv * VW;
+    if constexpr (VW == 4) *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(s);
+    else *o = *s;
+  }
+}
+
+// bwd: dx[B, n_in, D] = dy[B, a + b, D] scattered back, ZEROS in the cut rows (written here: no fill launch, no memset
+// node in a captured graph); dx_lp (optional) = the same rows in the compute dtype for the backward GEMMs.
+template <typename T, int VW>
+__global__ __launch_bounds__(256) void rows_cut_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
+                                                           T* __restrict__ dx_lp, int B, int n_in, int a, int b, int D) {
+  const unsigned dvn = D / VW, n_out = a + b;
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= (unsigned)n_in * dvn) return;
+  const unsigned l = idx / dvn, dv = idx - l * dvn;
+  const int lc = l < (unsigned)a ? (int)l : (l >= (unsigned)(n_in - b) ? (int)(l - (n_in - n_out)) : -1);
+  for (int img = blockIdx.y; img < B; img += gridDim.y) {
+    const long off = ((long)img * n_in + l) * D + dv * VW;
+    if constexpr (VW == 4) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (lc >= 0) v = *reinterpret_cast<const float4*>(dy + ((long)img * n_out + lc) * D + dv * 4);
+      *reinterpret_cast<float4*>(dx + off) = v;
+      if (dx_lp) {
+        if constexpr (sizeof(T) == 4) {
+          *reinterpret_cast<float4*>(dx_lp + off) = v;
+        } else {
+          bf16x4 t;
+          t[0] = (bf16_t)v.x; t[1] = (bf16_t)v.y; t[2] = (bf16_t)v.z; t[3] = (bf16_t)v.w;
+          *reinterpret_cast<bf16x4*>(dx_lp + off) = t;
+        }
+      }
+    } else {
+      const float v = lc >= 0 ? dy[((long)img * n_out + lc) * D + dv] : 0.f;
+      dx[off] = v;
+      if (dx_lp) dx_lp[off] = from_f32<T>(v);
+    }
+  }
+}
+
 // mean cross-entropy rows: loss_rows[b] = lse - logit[label]; dlogits = (softmax - onehot) * grad_scale
 // LS (label smoothing eps, nn.CrossEntropyLoss(label_smoothing=eps)): the target distribution is (1 - eps) * onehot +
 // eps / C, i.e. loss_rows[b] = lse - (1 - eps) * logit[label] - eps * mean_c(logit) and
@@ -1133,6 +1186,49 @@ extern "C" int favit_embed_prologue_bwd(const float* dx, void* dtok, int dtok_dt
     hipLaunchKernelGGL((embed_prologue_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, st, dx, (bf16_t*)dtok, dcls, dpos, B, N, D);
   else
     return FAVIT_ERR_INVALID;
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+static inline bool rows_cut_args_ok(int32_t B, int32_t n_in, int32_t a, int32_t b, int32_t D) {
+  // (one image's (row, column) pairs are indexed with 32 bits)
+  return B > 0 && n_in > 0 && D > 0 && a >= 0 && b >= 0 && a + b >= 1 && (long)a + b <= n_in && (long)n_in * D < (1L << 31);
+}
+
+static inline dim3 rows_cut_grid(int32_t B, long per_image) {
+  return dim3((unsigned)((per_image + 255) / 256), (unsigned)(B < 65535 ? B : 65535));
+}
+
+extern "C" int favit_rows_cut_fwd(const float* x, float* y, int32_t B, int32_t n_in, int32_t a, int32_t b, int32_t D,
+                                  void* stream) {
+  if (!x || !y || !rows_cut_args_ok(B, n_in, a, b, D)) return FAVIT_ERR_INVALID;
+  const bool v4 = (D & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  const dim3 grid = rows_cut_grid(B, (long)(a + b) * (v4 ? D / 4 : D));
+  if (v4)
+    hipLaunchKernelGGL(rows_cut_fwd_kernel<4>, grid, dim3(256), 0, as_stream(stream), x, y, B, n_in, a, b, D);
+  else
+    hipLaunchKernelGGL(rows_cut_fwd_kernel<1>, grid, dim3(256), 0, as_stream(stream), x, y, B, n_in, a, b, D);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_rows_cut_bwd(const float* dy, float* dx, void* dx_lp, int lp_dtype, int32_t B, int32_t n_in,
+                                  int32_t a, int32_t b, int32_t D, void* stream) {
+  if (!dy || !dx || !rows_cut_args_ok(B, n_in, a, b, D)) return FAVIT_ERR_INVALID;
+  if (dx_lp && lp_dtype != FAVIT_F32 && lp_dtype != FAVIT_BF16) return FAVIT_ERR_INVALID;
+  const bool v4 = (D & 3) == 0 && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(dx_lp) & 7) == 0 && (lp_dtype != FAVIT_F32 || (reinterpret_cast<uintptr_t>(dx_lp) & 15) == 0);
+  const dim3 grid = rows_cut_grid(B, (long)n_in * (v4 ? D / 4 : D));
+  hipStream_t st = as_stream(stream);
+  const bool f32 = !dx_lp || lp_dtype == FAVIT_F32;
+  if (v4 && f32)
+    hipLaunchKernelGGL((rows_cut_bwd_kernel<float, 4>), grid, dim3(256), 0, st, dy, dx, (float*)dx_lp, B, n_in, a, b, D);
+  else if (v4)
+    hipLaunchKernelGGL((rows_cut_bwd_kernel<bf16_t, 4>), grid, dim3(256), 0, st, dy, dx, (bf16_t*)dx_lp, B, n_in, a, b, D);
+  else if (f32)
+    hipLaunchKernelGGL((rows_cut_bwd_kernel<float, 1>), grid, dim3(256), 0, st, dy, dx, (float*)dx_lp, B, n_in, a, b, D);
+  else
+    hipLaunchKernelGGL((rows_cut_bwd_kernel<bf16_t, 1>), grid, dim3(256), 0, st, dy, dx, (bf16_t*)dx_lp, B, n_in, a, b, D);
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }

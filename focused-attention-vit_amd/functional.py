@@ -492,9 +492,11 @@ _WG = {"list": None, "blocks": 0, "every": 1, "bytes": 0}
 _WG_HOLD_BYTES = int(float(os.environ.get("FAVIT_WGRAD_HOLD_MB", "384")) * (1 << 20))
 
 
-def begin_wgrads() -> None:
+def begin_wgrads(per_block: bool = False) -> None:
+    """per_block: the token count differs from block to block (CLS-only encoders) and a grouped launch shares it, so
+    there is nothing to group across blocks."""
     every = 4 if _STATE["grad_ready"] is not None else K.GROUP_MAX // 4
-    if _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
+    if per_block or _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
         every = 1                             # (side-stream mode and the A/B switch: one launch per block, as in round 3)
     _WG.update(list=[], blocks=0, every=every, bytes=0)
 
@@ -554,7 +556,11 @@ def flush_deferred() -> None:
     fold, ln = _DEFER["fold"], _DEFER["ln"]
     _DEFER["fold"], _DEFER["ln"] = [], []
     if ln:
-        K.reduce_rows_multi([e[:3] for e in ln])
+        by_shape = {}                         # (one launch per shape of the partial sums: it follows the row count)
+        for e in ln:
+            by_shape.setdefault(tuple(e[0].shape), []).append(e)
+        for es in by_shape.values():
+            K.reduce_rows_multi([e[:3] for e in es])
         for e in ln:
             _ready(*e[3])
     by_h = {}
@@ -1059,24 +1065,68 @@ class BlockSpec:
         self.n = len(self.names)
 
 
+def cls_plan(L: int, W: int, depth: int) -> List[Optional[Tuple[int, int]]]:
+    """Token rows each block of an all-MHLA encoder has to compute when only row 0 (CLS) of the last block is read
+    (FinalNormOp).  Row i of a window-W block reads keys [i - h, i + h] (h = W // 2) plus pad copies of key L - 1 (rows
+    whose window is cut at 0) or key 0 (rows whose window is cut at L), so the field grows by h rows at each end per
+    block going down: block k (1-based) of `depth`, j = depth - k, needs its input rows [0, 1 + h (j + 1)) and
+    [L - (1 + h j), L).  Entry k - 1 is that (head, tail) pair, or None where the two ranges cover the sequence.
+    Stored head rows first, tail rows after them, a block computes the needed rows correctly with the unchanged window
+    rule at L' = head + tail (tests/test_cls_only_plan.py checks both against the oracle)."""
+    h = W // 2
+    plan: List[Optional[Tuple[int, int]]] = []
+    for k in range(1, depth + 1):
+        j = depth - k
+        a, b = 1 + h * (j + 1), 1 + h * j
+        plan.append(None if a + b >= L else (a, b))
+    return plan
+
+
+def cls_only_cuts(specs: Sequence["BlockSpec"], L: int, mask, training: bool):
+    """The cls_plan of an encoder whose only consumer is the CLS row, or None where the full path has to run: a block
+    that is not MHLA + MLP, differing windows, an attention mask, a dropout that is active in this mode (the masks are
+    indexed by element position: a compact layout would draw other masks), fp8 mode (its quantisation sites hand
+    tensors of the full shape from kernel to kernel), FAVIT_NO_PRUNE=1 (A/B switch, read at each call), or a sequence
+    so short that every block needs all rows."""
+    if os.environ.get("FAVIT_NO_PRUNE") or mask is not None or not specs or _STATE.get("fp8"):
+        return None
+    if not all(isinstance(s.attn, MHLAChain) and isinstance(s.mlp, MLPChain) for s in specs):
+        return None
+    if len({s.attn.W for s in specs}) != 1:
+        return None
+    if training and any(s.attn.p_attn > 0 or s.attn.p_proj > 0 or s.mlp.p > 0 for s in specs):
+        return None
+    plan = cls_plan(L, specs[0].attn.W, len(specs))
+    return plan if any(c is not None for c in plan) else None
+
+
 class EncoderOp:
     """A stack of pre-LN blocks on the fp32 residual stream [B, L, D]:
-    x += attn(LN1(x)); x += mlp(LN2(x))."""
+    x += attn(LN1(x)); x += mlp(LN2(x)).
+    cuts (CLS-only mode, see cls_plan): per block the (head, tail) rows it runs on, or None for all rows.  The stream
+    is cut to a block's rows in front of it (favit_rows_cut_fwd), the block runs on the compact [B, n, D] tensor with
+    L = n throughout, and the output keeps the last block's rows; backward expands at the same points
+    (favit_rows_cut_bwd)."""
 
-    def __init__(self, blocks: List[BlockSpec], mask=None, training=False):
+    def __init__(self, blocks: List[BlockSpec], mask=None, training=False, cuts=None):
         self.blocks, self.mask, self.training = blocks, mask, training
+        self.cuts = list(cuts) if cuts is not None else None
+        if self.cuts is not None and (len(self.cuts) != len(blocks) or mask is not None):
+            raise ValueError("cuts: one entry per block, and no attention mask")
 
     def fwd(self, ins, prm):
         (x,) = ins
         B, L, D = x.shape
         M = B * L
+        L_in = L
         cdt = get_compute_dtype()
         x = _as_f32(x).reshape(M, D)
         tapes = []
         # short token counts, bf16: the two LayerNorms of a block ride in the A-operand staging of the qkv / fc1
         # projections (favit_ln_gemm; the library declines shapes beyond the 64-row kernel's regime, and
         # lin_fwd_ln then issues the two launches)
-        fuse = _LN_FUSE and cdt == torch.bfloat16 and get_compute_mode() == "bf16" and M <= 16384 and D % 64 == 0 and D <= 512
+        # (evaluated per block: a CLS-only encoder's blocks run on different row counts; the switch is off by default)
+        fuse_ok = _LN_FUSE and cdt == torch.bfloat16 and get_compute_mode() == "bf16" and D % 64 == 0 and D <= 512
         # the latent_proj folds only depend on parameters: all MHLA blocks of equal geometry in ONE launch
         pre = [None] * len(self.blocks)
         idx, fp, off = [], [], 0
@@ -1097,6 +1147,14 @@ class EncoderOp:
             pa = p[2:2 + na]
             g2, b2 = p[2 + na], p[3 + na]
             pm = p[4 + na:]
+            cut = None
+            if self.cuts is not None and self.cuts[bi] is not None and sum(self.cuts[bi]) < L:
+                ca, cb = self.cuts[bi]
+                x = K.rows_cut_fwd(x, B, L, ca, cb, D).reshape(B * (ca + cb), D)
+                cut = (L, ca, cb)
+                L = ca + cb
+                M = B * L
+            fuse = fuse_ok and M <= 16384
             if fuse and isinstance(bs.attn, (MHLAChain, DenseChain)):
                 o1 = [None, None, None]
                 kw = {"pre": pre[bi]} if pre[bi] is not None else {}
@@ -1115,29 +1173,30 @@ class EncoderOp:
             else:
                 xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
                 x2, sm = bs.mlp.fwd(xn2, pm, x1, self.training)
-            tapes.append((x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa, pm)))
+            tapes.append((x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa, pm), cut))
             x = x2
-        return x.reshape(B, L, D), (tapes, B, L, D)
+        return x.reshape(B, L, D), (tapes, B, L_in, D)
 
     def bwd(self, saved, dy, needs):
         tapes, B, L, D = saved
-        M = B * L
-        g = dy.reshape(M, D)
+        g = dy.reshape(-1, D)
         g_lp = _as_cdt(g)
         grads = []
-        begin_wgrads()
+        begin_wgrads(per_block=any(tp[11] is not None for tp in tapes))
         begin_deferred()
         begin_zero_pool(sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)), dy.device)
 
-        def ln_bwd(dxn, xin, gam, bet, mu, rs, dres, pd, q8=None):
+        def ln_bwd(dxn, xin, gam, bet, mu, rs, dres, pd, q8=None, want_lp=True):
             """LayerNorm backward of the stream; the dgamma / dbeta fold joins the deferred batch when the parameters own
-            gradient buffers (the fused-optimizer flow).  q8: the low-precision copy also leaves quantised (fp8 mode)."""
+            gradient buffers (the fused-optimizer flow).  q8: the low-precision copy also leaves quantised (fp8 mode).
+            want_lp=False: a row cut follows, and favit_rows_cut_bwd writes the copy of the expanded gradient."""
+            M = xin.shape[0]
             if not gam.requires_grad and not bet.requires_grad:      # frozen layer: no dgamma / dbeta fold at all
-                return K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=True, lp_drop=pd, frozen=True, q8=q8)
+                return K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, lp_drop=pd, frozen=True, q8=q8)
             tg_, tb_ = _gt(gam), _gt(bet)
             lst = _DEFER["ln"] if (_DEFER["on"] and tg_ is not None and tb_ is not None) else None
             n0 = len(lst) if lst is not None else 0
-            out = K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=True, dg_out=tg_, db_out=tb_,
+            out = K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, dg_out=tg_, db_out=tb_,
                                   lp_drop=pd, defer=lst, q8=q8)
             if lst is not None:
                 lst[n0] = lst[n0] + ((gam, bet),)
@@ -1151,7 +1210,7 @@ class EncoderOp:
             order = list(zip(reversed(self.blocks), reversed(tapes)))
             premasked = False
             for bi, (bs, tp) in enumerate(order):
-                x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa_, _) = tp
+                x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa_, _), cut = tp
                 dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
                 pd = bs.attn.out_dropout(sa) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
                 # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
@@ -1167,7 +1226,15 @@ class EncoderOp:
                     pd = nbs.mlp.out_dropout(ntp[9])
                     q8n = _q8_request(nbs.mlp, ntp[10][1], "bwd", D)       # the next block's fc2 input-gradient GEMM
                 premasked = pd[0] > 0
-                g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd, q8=q8n)
+                g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd, q8=q8n, want_lp=cut is None)
+                if cut is not None:
+                    # this block ran on its (head, tail) rows: back to the rows of the block below, zeros in between,
+                    # with the compute-dtype copy that block's backward GEMMs read written in the same pass
+                    n_in, ca, cb = cut
+                    more = bi + 1 < len(order) and g.dtype != dxn1.dtype
+                    g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=dxn1.dtype if more else None)
+                    g = g.reshape(B * n_in, D)
+                    g_lp = g_lp.reshape(B * n_in, D) if g_lp is not None else g
                 if flush_wgrads(force=False) and _STATE["grad_ready"] is not None:
                     flush_deferred()
                 if not _SIDE["enabled"]:

@@ -635,6 +635,28 @@ def embed_prologue_bwd(dx, B, N, D, tok_dtype, want_pos=True):
     return dtok, dcls, dpos
 
 
+def rows_cut_fwd(x, B, n_in, a, b, D):
+    """x fp32 [B, n_in, D] (contiguous) -> [B, a + b, D]: the first a and the last b rows of every image."""
+    require_gpu(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != B * n_in * D:
+        raise ValueError("rows_cut_fwd expects a contiguous fp32 [B, n_in, D] tensor")
+    y = torch.empty((B, a + b, D), dtype=torch.float32, device=x.device)
+    _abi.check(_abi.lib().favit_rows_cut_fwd(_p(x), _p(y), B, n_in, a, b, D, _st()), "favit_rows_cut_fwd")
+    return y
+
+
+def rows_cut_bwd(dy, B, n_in, a, b, D, lp_dtype=None):
+    """dy fp32 [B, a + b, D] -> (dx fp32 [B, n_in, D] with zeros in the cut rows, its lp_dtype copy or None)."""
+    require_gpu(dy)
+    if dy.dtype != torch.float32 or not dy.is_contiguous() or dy.numel() != B * (a + b) * D:
+        raise ValueError("rows_cut_bwd expects a contiguous fp32 [B, a + b, D] tensor")
+    dx = torch.empty((B, n_in, D), dtype=torch.float32, device=dy.device)
+    lp = torch.empty((B, n_in, D), dtype=lp_dtype, device=dy.device) if lp_dtype is not None else None
+    _abi.check(_abi.lib().favit_rows_cut_bwd(_p(dy), _p(dx), _p(lp), dt(lp) if lp is not None else F32, B, n_in, a, b, D,
+                                             _st()), "favit_rows_cut_bwd")
+    return dx, lp
+
+
 def dropout(x, p, seed):
     y = torch.empty_like(x)
     _abi.check(_abi.lib().favit_dropout(_p(x), _p(y), dt(x), x.numel(), p, seed, _st()), "favit_dropout")

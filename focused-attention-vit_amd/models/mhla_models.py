@@ -59,7 +59,9 @@ class PretrainedViTWithMHLA(nn.Module):
         tok = self.patch_embed(x)
         x = F.run(F.PrologueOp(True), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
-        x = run_encoder(self.blocks, x, None, self.training)
+        # only the CLS row is read below: the blocks compute just the rows it can see (functional.cls_plan)
+        x = run_encoder(self.blocks, x, None, self.training,
+                        cls_only=not (self.training and self.pos_drop.p > 0))
         return F.run(F.FinalNormOp(), [x], [self.norm.weight, self.norm.bias])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -109,7 +111,8 @@ class PretrainedSPPPViTWithMHLA(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         t = sppp_tokens(self, x)
-        t = run_encoder(self.blocks, t, None, self.training)
+        t = run_encoder(self.blocks, t, None, self.training,
+                        cls_only=not (self.training and self.pos_embed.dropout.p > 0))
         t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
         return F.run(F.LinearOp(), [t], [self.head.weight, self.head.bias])
 

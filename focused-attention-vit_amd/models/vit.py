@@ -101,23 +101,28 @@ class TransformerBlock(nn.Module):
         return F.run(F.EncoderOp([spec], None, self.training), [x], params(self, spec.names))
 
 
-def run_encoder(blocks, x, mask, training):
+def run_encoder(blocks, x, mask, training, cls_only=False):
     """All blocks of a model as ONE autograd node (no per-block fp32<->bf16 gradient casts) -- or, while
     functional.encoder_segments(n) is active (train.GraphedStep with backward segments), as n consecutive nodes cut
-    apart at detached boundary tensors, so that backward can be run, and captured, segment by segment."""
+    apart at detached boundary tensors, so that backward can be run, and captured, segment by segment.
+    cls_only: the caller reads nothing but row 0 of the result (FinalNormOp).  Where functional.cls_only_cuts allows
+    it, every block then computes only the token rows that row can see, and the result is [B, n, D] with the last
+    block's n rows (row 0 first) instead of [B, L, D]."""
     blocks = list(blocks)
     nseg = max(1, min(F.get_encoder_segments(), len(blocks)))
     m = F._mask_u8(mask)
     per = (len(blocks) + nseg - 1) // nseg
+    all_specs = [b._spec() for b in blocks]
+    cuts = F.cls_only_cuts(all_specs, x.shape[1], m, training) if cls_only else None
     for i in range(0, len(blocks), per):
         grp = blocks[i:i + per]
-        specs = [b._spec() for b in grp]
+        specs = all_specs[i:i + per]
         prm = []
         for b, s in zip(grp, specs):
             prm += params(b, s.names)
         if i:
             x = F.note_segment_boundary(x)        # the next node starts a fresh autograd graph at a leaf copy of x
-        x = F.run(F.EncoderOp(specs, m, training), [x], prm)
+        x = F.run(F.EncoderOp(specs, m, training, cuts=None if cuts is None else cuts[i:i + per]), [x], prm)
     return x
 
 

@@ -89,7 +89,9 @@ class VisionTransformerMHLA(nn.Module):
         tok = self.patch_embed(x)
         x = F.run(F.PrologueOp(True), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
-        x = run_encoder(self.blocks, x, None, self.training)
+        # only the CLS row is read below: MHLA stacks compute just the rows it can see (functional.cls_plan)
+        x = run_encoder(self.blocks, x, None, self.training,
+                        cls_only=not (self.training and self.pos_drop.p > 0))
         return F.run(F.FinalNormOp(), [x], [self.norm.weight, self.norm.bias])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

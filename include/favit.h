@@ -420,6 +420,15 @@ int favit_embed_prologue_fwd(const float* tok, const float* cls, const float* po
 int favit_embed_prologue_bwd(const float* dx, void* dtok, int dtok_dtype, float* dcls, float* dpos, int32_t B,
                              int32_t N, int32_t D, void* stream);
 
+/* Row cut of the fp32 residual stream (CLS-only encoders: only the token rows the CLS head can see are computed,
+ * DESIGN.md section 9).  Every image keeps its first a and its last b rows, stored one after the other; a + b <= n_in.
+ * fwd: y[B, a + b, D] from x[B, n_in, D].
+ * bwd: dx[B, n_in, D] = dy[B, a + b, D] scattered back with zeros in the cut rows (written by the kernel itself);
+ *      dx_lp (may be NULL; lp_dtype FAVIT_F32 or FAVIT_BF16) receives the same values in the compute dtype. */
+int favit_rows_cut_fwd(const float* x, float* y, int32_t B, int32_t n_in, int32_t a, int32_t b, int32_t D, void* stream);
+int favit_rows_cut_bwd(const float* dy, float* dx, void* dx_lp, int lp_dtype, int32_t B, int32_t n_in, int32_t a,
+                       int32_t b, int32_t D, void* stream);
+
 /* Inverted dropout with a counter-based RNG (nn.Dropout sites, models/vit.py:136,138,
  * 102, mhla.py:159); the mask is recomputed from (seed, index) in backward. */
 int favit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t seed, void* stream);
