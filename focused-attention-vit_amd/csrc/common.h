@@ -129,7 +129,9 @@ __device__ __forceinline__ float dgelu_fast(float x) {
 // Round 4: ONE 32-bit draw serves the TWO elements 2i and 2i + 1 (its low / high 16 bits against a 16-bit threshold, so
 // p is realised to 1 / 65536): the quarter-rate multiplies of the draw were the bulk of a dropout epilogue's VALU work
 // (fc1 forward at cfg2: +23 us per launch with dropout 0.1, dH +19 us; now +8 / +10), and the vector epilogues walk pairs.
-// tests/test_gpu_kernels.py checks keep rates and the absence of correlation across lags, strides and seeds.
+// tests/test_gpu_kernels.py checks keep rates and the absence of correlation across lags, strides and seeds;
+// tests/_dropout_ref.py restates the draw on the host and tests/test_gpu_dropout_masks.py checks it bit for bit against
+// favit_dropout, then every kernel that draws against float64 references built with the explicit mask.
 __device__ __forceinline__ uint32_t favit_mix_u32(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7FEB352Du;

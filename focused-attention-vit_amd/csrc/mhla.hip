@@ -2095,8 +2095,8 @@ int attn_entry(bool bwd, const void* qkv, const void* dout, void* out, const uin
     return FAVIT_OK;
   }
   // bf16 backward on MFMA, "two owner passes" formulation (mhla_bwd_mfma2_kernel): balanced row blocks of <= 64,
-  // no dS / P tables.  FAVIT_MHLA_BWD_TABLES selects the older table formulation (72 KiB of LDS), FAVIT_MHLA_VALU
-  // the 8-lanes-per-row kernel; all three pass the same tests.
+  // no dS / P tables.  FAVIT_MHLA_VALU, FAVIT_MHLA_BWD_TABLES and FAVIT_MHLA_BWD_MFMA all turn this branch off, and the
+  // call then reaches the 8-lanes-per-row kernel below (mhla_bwd_kernel, through dispatch_dpl).
   if (bwd && dtype == FAVIT_BF16 && (hd == 32 || hd == 64 || hd == 128) && (W <= 7 || (W <= 11 && L > 16)) &&
       getenv("FAVIT_MHLA_VALU") == nullptr && getenv("FAVIT_MHLA_BWD_MFMA") == nullptr && getenv("FAVIT_MHLA_BWD_TABLES") == nullptr) {
     const int h = W / 2;
@@ -2145,9 +2145,9 @@ int attn_entry(bool bwd, const void* qkv, const void* dout, void* out, const uin
       return FAVIT_OK;
     }
   }
-  // The table formulation of the MFMA backward (opt-in: FAVIT_MHLA_BWD_MFMA=1 or FAVIT_MHLA_BWD_TABLES=1): measured
-  // 189 us at the bench shape against 131 us for the 8-lanes-per-row kernel (72 KiB of LDS allow only two
-  // workgroups per CU and every phase is latency-bound).
+  // The table formulation of the MFMA backward (mhla_bwd_mfma_kernel) is NOT launched from here or anywhere else, and
+  // no test runs it: its two switches select the 8-lanes-per-row kernel.  (It measured 189 us at the bench shape
+  // against 131 us for that kernel: 72 KiB of LDS allow only two workgroups per CU and every phase is latency-bound.)
   if (dtype == FAVIT_F32) return W <= 7 ? dispatch_dpl<float, 7>(bwd, a, st) : dispatch_dpl<float, 15>(bwd, a, st);
   if (dtype == FAVIT_BF16) return W <= 7 ? dispatch_dpl<bf16_t, 7>(bwd, a, st) : dispatch_dpl<bf16_t, 15>(bwd, a, st);
   return FAVIT_ERR_INVALID;

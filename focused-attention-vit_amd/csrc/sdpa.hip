@@ -417,10 +417,12 @@ __global__ __launch_bounds__(320) void sdpa_kernel(SdpaArgs a) {      // 4 or 5 
   };
   if (MODE == 0) {
     l_run = quad16_sum(l_run);
-    const float inv = 1.0f / l_run;                    // a fully masked row: 0 * inf = NaN, as torch's softmax
+    // a query row with every key masked (l_run == 0): o = 0 and lse = -inf (favit.h); 1 / 0 would give 0 * inf = NaN,
+    // and through delta = dO . O a NaN in every dk / dv row of that (batch, head)
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
     if (on < Lo) {
       store(a.out0, a.vo0, acc1, inv);
-      if (g == 0 && blockIdx.z == 0) a.lse[zq + on] = m_run + __logf(l_run);
+      if (g == 0 && blockIdx.z == 0) a.lse[zq + on] = l_run > 0.f ? m_run + __logf(l_run) : -INFINITY;
     }
   } else if (on < Lo) {
     store(a.out0, a.vo0, acc0, 1.0f);

@@ -132,8 +132,8 @@ def gemm(A, B, Cc, M, N, K, lda, ldb, ldc, *, a_kmajor=True, b_kmajor=True, bias
     GEMM_TRACE.append((e0, e1, 2.0 * M * N * K * batch, key, (M, N, K, batch), _abi.lib().favit_gemm_last_kernel().decode()))
 
 
-def ln_gemm(x, ldx, gamma, beta, w, out, M, N, D, *, bias=None, act=ACT_NONE, aux_out=None, residual=None,
-            dropout_p=0.0, dropout_seed=0, eps=1e-5):
+def ln_gemm(x, ldx, gamma, beta, w, out, M, N, D, *, bias=None, act=ACT_NONE, aux_in=None, ld_aux_in=0, aux_out=None,
+            residual=None, dropout_p=0.0, dropout_seed=0, eps=1e-5):
     """out = epilogue(LayerNorm(x) @ w^T) in one launch (favit_ln_gemm); returns (xn bf16 [M, D], mean, rstd), or None
     when the library declines the shape (the caller then runs layernorm_fwd + gemm)."""
     require_gpu(x, gamma, beta, w, out)
@@ -143,11 +143,12 @@ def ln_gemm(x, ldx, gamma, beta, w, out, M, N, D, *, bias=None, act=ACT_NONE, au
     d.A = None
     d.B, d.C = w.data_ptr(), out.data_ptr()
     d.bias = bias.data_ptr() if bias is not None else None
+    d.aux_in = aux_in.data_ptr() if aux_in is not None else None
     d.aux_out = aux_out.data_ptr() if aux_out is not None else None
     d.residual = residual.data_ptr() if residual is not None else None
     d.M, d.N, d.K = M, N, D
     d.lda, d.ldb, d.ldc = D, w.stride(0), out.stride(0)
-    d.ld_aux_out, d.ld_res = N, N
+    d.ld_aux_in, d.ld_aux_out, d.ld_res = ld_aux_in, N, N
     d.batch, d.batch_inner = 1, 1
     d.a_kmajor, d.b_kmajor = 1, 1
     d.in_dtype, d.out_dtype = BF16, dt(out)

@@ -380,6 +380,9 @@ int favit_slic_connect(const uint8_t* labels, int32_t* ws_comp, int32_t* ws_aux,
  * mask (uint8, 0 = -inf, NULL = none) is addressed mask[b*m_sb + q*m_sq + k]  (key-keep [B,Lk]: m_sq = 0).
  * fwd writes o and lse [B*H, Lq] (row log-sum-exp of the scaled, masked scores); bwd needs q, k, v, o, dout,
  * lse and a workspace delta [B*H, Lq], and writes dq, dk, dv (probabilities are recomputed; deterministic).
+ * A query row whose keys are ALL masked (PyTorch's softmax gives NaN there): its row of o is 0, its lse is -inf, and
+ * in bwd it gets dq = 0 and adds nothing to dk or dv (the recomputed probabilities of masked entries are 0 whatever
+ * lse holds, and delta = dO . O = 0); no other row is affected and nothing non-finite is written to o, dq, dk or dv.
  * dropout: inverted, counter-based on (seed, ((b*H + h)*Lq + q)*Lk + k), the same draw in fwd and bwd.
  * dtype FAVIT_BF16 (bf16 MFMA, fp32 accumulate / softmax) or FAVIT_F32 (exact-fp32 MFMA); hd % 16 == 0.
  * ---------------------------------------------------------------------------------- */
