@@ -114,6 +114,10 @@ _SIGS = {
     "favit_grad_norm_workspace": ([], C.c_int64),
     "favit_grad_norm": ([i32, vp, vp, f32, f32, vp, vp, vp, i64, vp], C.c_int),
     "favit_adamw_clip": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, vp], C.c_int),
+    "favit_adamw_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp], C.c_int),
+    "favit_adamw_clip_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, f32, vp],
+                             C.c_int),
+    "favit_swap_params": ([vp, vp, vp, i64, vp], C.c_int),
 }
 
 _lib = None

@@ -673,11 +673,16 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
 // CLIP (favit_adamw_clip): the gradient is also multiplied by the DEVICE scalar *coef (favit_grad_norm's clip
 // coefficient, read when the kernel executes: no host sync between the norm and the update).  With `skip` set and a
 // non-finite coefficient -- the norm pass met a non-finite gradient -- the launch writes nothing but the health word.
-template <bool CLIP>
+// EMA (favit_adamw_ema / favit_adamw_clip_ema): the launch also moves an exponential moving average of the
+// parameters towards the value it has just computed, ema = d * ema + (1 - d) * p_new, while p_new is in a register:
+// one 4-byte load and one 4-byte store per element on top of the update's 30 bytes, no second pass over p.  A skipped
+// launch returns before any store, so the average stays as it was too.  The two trailing arguments are not read by
+// the <CLIP, false> instantiations, which compile to what they were before the average existed.
+template <bool CLIP, bool EMA>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, bf16_t* __restrict__ p_lp, long n, float lr, float b1, float b2,
                              float eps, float wd, float bc1, float bc2, float gscale, unsigned* __restrict__ health,
-                             const float* __restrict__ coef, int skip) {
+                             const float* __restrict__ coef, int skip, float* __restrict__ ema, float ema_decay) {
   float cf = 1.0f;
   if constexpr (CLIP) {
     cf = *coef;
@@ -704,6 +709,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     const float pi = __builtin_fmaf(decay, p[i], -((step * mi) / __builtin_fmaf(rbc2, sqrtf(vi), eps)));
     p[i] = pi; m[i] = mi; v[i] = vi;
     if (p_lp) p_lp[i] = (bf16_t)pi;
+    // (product rounded, then one fused multiply-add: the two roundings the tests' float64 bound allows)
+    if constexpr (EMA) ema[i] = __builtin_fmaf(ema_decay, ema[i], (1.0f - ema_decay) * pi);
     bad_g |= !isfinite(gi);
     bad_p |= !isfinite(pi);
   }
@@ -717,6 +724,17 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     if (f && !(atomicOr(health, f) & 6u)) health[2] = health[3] + 1;
     __syncthreads();
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(health + 3, 1u);   // (stream order: one AdamW launch at a time)
+  }
+}
+
+// favit_swap_params: a[i] <-> b[i] over two flat fp32 buffers, and the bf16 mirror of the new a.  18 bytes per
+// element (8 read, 8 + 2 written), HBM-bound; every element is read and written by the one thread that owns it.
+__global__ void swap_params_kernel(float* __restrict__ a, float* __restrict__ b, bf16_t* __restrict__ a_lp, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float ai = a[i], bi = b[i];
+    a[i] = bi;
+    b[i] = ai;
+    if (a_lp) a_lp[i] = (bf16_t)bi;
   }
 }
 
@@ -1257,7 +1275,7 @@ extern "C" int favit_adamw(float* p, const float* g, float* m, float* v, void* p
                            float grad_scale, void* stream) {
   if (!p || !g || !m || !v || n < 0) return FAVIT_ERR_INVALID;
   if (n == 0) return FAVIT_OK;
-  hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), (const float*)nullptr, 0);
+  hipLaunchKernelGGL((adamw_kernel<false, false>), dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), (const float*)nullptr, 0, (float*)nullptr, 0.0f);
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }
@@ -1269,7 +1287,45 @@ extern "C" int favit_adamw_clip(float* p, const float* g, float* m, float* v, vo
   if (reinterpret_cast<uintptr_t>(coef) & 3) return FAVIT_ERR_ALIGN;
   if (n == 0) return FAVIT_OK;                       // (an empty group: nothing to read, whatever its pointers)
   if (!p || !g || !m || !v) return FAVIT_ERR_INVALID;
-  hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), coef, (int)(skip_nonfinite != 0));
+  hipLaunchKernelGGL((adamw_kernel<true, false>), dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), coef, (int)(skip_nonfinite != 0), (float*)nullptr, 0.0f);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, int64_t n,
+                               float lr, float beta1, float beta2, float eps, float weight_decay, float bias_c1,
+                               float bias_c2, float grad_scale, float ema_decay, void* stream) {
+  if (n < 0 || !(ema_decay >= 0.f && ema_decay <= 1.f)) return FAVIT_ERR_INVALID;
+  if (n == 0) return FAVIT_OK;
+  if (!p || !g || !m || !v || !ema) return FAVIT_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(ema) & 3) return FAVIT_ERR_ALIGN;
+  hipLaunchKernelGGL((adamw_kernel<false, true>), dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), (const float*)nullptr, 0, ema, ema_decay);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_adamw_clip_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, int64_t n,
+                                    float lr, float beta1, float beta2, float eps, float weight_decay, float bias_c1,
+                                    float bias_c2, float grad_scale, const float* coef, int32_t skip_nonfinite,
+                                    float ema_decay, void* stream) {
+  if (n < 0 || !coef || !(ema_decay >= 0.f && ema_decay <= 1.f)) return FAVIT_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(coef) & 3) return FAVIT_ERR_ALIGN;
+  if (n == 0) return FAVIT_OK;
+  if (!p || !g || !m || !v || !ema) return FAVIT_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(ema) & 3) return FAVIT_ERR_ALIGN;
+  hipLaunchKernelGGL((adamw_kernel<true, true>), dim3(grid_for(n)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2, grad_scale, favit_health_ptr_(), coef, (int)(skip_nonfinite != 0), ema, ema_decay);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_swap_params(float* a, float* b, void* a_bf16, int64_t n, void* stream) {
+  if (n < 0) return FAVIT_ERR_INVALID;
+  if (n == 0) return FAVIT_OK;
+  if (!a || !b || a == b) return FAVIT_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(b) & 3) ||
+      (reinterpret_cast<uintptr_t>(a_bf16) & 1))
+    return FAVIT_ERR_ALIGN;
+  hipLaunchKernelGGL(swap_params_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), a, b, (bf16_t*)a_bf16, (long)n);
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }

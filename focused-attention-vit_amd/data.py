@@ -129,6 +129,26 @@ class DeviceTransform:
         self.std = (C.c_float * 3)(*[float(s) for s in std])
         self.rng = np.random.RandomState(seed)
 
+    # ---- checkpoint state: the generator of the random crops / flips (plain containers and one tensor) ----
+    def state_dict(self) -> Dict:
+        name, keys, pos, has_gauss, cached = self.rng.get_state()
+        return {"kind": self.kind, "bit_generator": str(name), "keys": torch.from_numpy(keys.astype(np.int64)),
+                "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+    def check_state_dict(self, state: Dict) -> None:
+        for k in ("bit_generator", "keys", "pos", "has_gauss", "cached_gaussian"):
+            if k not in state:
+                raise ValueError(f"DeviceTransform state: entry '{k}' is missing")
+        if state["bit_generator"] != "MT19937" or tuple(state["keys"].shape) != (624,):
+            raise ValueError("DeviceTransform state: 'keys' is not the 624-word state of an MT19937 generator")
+        if state.get("kind", self.kind) != self.kind:
+            raise ValueError(f"DeviceTransform state: 'kind' is {state['kind']!r}, the transform is {self.kind!r}")
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.check_state_dict(state)
+        self.rng.set_state(("MT19937", state["keys"].numpy().astype(np.uint32), int(state["pos"]),
+                            int(state["has_gauss"]), float(state["cached_gaussian"])))
+
     # ---- per-image parameter rows (see include/favit.h: favit_image_transform) ----
     def params(self, B: int, H, W) -> np.ndarray:
         """H, W: the source size, scalars for a uniform batch or [B] arrays for a ragged one (every row is then drawn
@@ -301,6 +321,25 @@ class DeviceLoader:
 
     def __len__(self):
         return len(self.src)
+
+    # ---- checkpoint state, between epochs: the transform's generator and the source's shuffle epoch ----
+    def state_dict(self) -> Dict:
+        return {"transform": self.tf.state_dict(),
+                "batches": self.src.state_dict() if hasattr(self.src, "state_dict") else None}
+
+    def check_state_dict(self, state: Dict) -> None:
+        for k in ("transform", "batches"):
+            if k not in state:
+                raise ValueError(f"DeviceLoader state: entry '{k}' is missing")
+        self.tf.check_state_dict(state["transform"])
+        if state["batches"] is not None and hasattr(self.src, "check_state_dict"):
+            self.src.check_state_dict(state["batches"])
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.check_state_dict(state)
+        self.tf.load_state_dict(state["transform"])
+        if state["batches"] is not None and hasattr(self.src, "load_state_dict"):
+            self.src.load_state_dict(state["batches"])
 
     def _stage_ragged_host(self, slot: int, rb: RaggedBatch, labels: torch.Tensor):
         """Pinned views holding a ragged host batch.  The staging buffers only ever grow (to the largest batch seen), and

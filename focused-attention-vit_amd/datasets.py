@@ -230,6 +230,20 @@ class _Batches:
         n = len(self.ds)
         return n // self.bs if self.drop_last else (n + self.bs - 1) // self.bs
 
+    # checkpoint state: the shuffle of epoch e is a function of (seed, e) alone
+    def state_dict(self) -> Dict[str, int]:
+        return {"epoch": int(self.epoch), "seed": self.seed}
+
+    def check_state_dict(self, state: Dict[str, int]) -> None:
+        if "epoch" not in state or int(state["epoch"]) < 0:
+            raise ValueError("batches state: 'epoch' is missing or negative")
+        if self.shuffle and int(state.get("seed", self.seed)) != self.seed:
+            raise ValueError(f"batches state: 'seed' is {state['seed']}, this object shuffles with {self.seed}")
+
+    def load_state_dict(self, state: Dict[str, int]) -> None:
+        self.check_state_dict(state)
+        self.epoch = int(state["epoch"])
+
     def _chunks(self) -> List[np.ndarray]:
         n = len(self.ds)
         order = np.random.RandomState([self.seed, self.epoch]).permutation(n) if self.shuffle else np.arange(n)

@@ -105,21 +105,41 @@ def evaluate(model, loader: Iterable, batch_size: Optional[int] = None) -> Dict[
 
 
 def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer, epochs: int,
-        log: Callable[[str], None] = print, label_smoothing: float = 0.0, schedule=None) -> Dict[str, object]:
+        log: Callable[[str], None] = print, label_smoothing: float = 0.0, schedule=None,
+        checkpoint: Optional[str] = None, checkpoint_every: int = 1, resume: bool = False,
+        eval_ema: bool = False) -> Dict[str, object]:
     """The reference's epoch loop (experiments/mhla_pretrained.py:350-420) with device-side statistics: one host
     sync per EPOCH.  optimizer: train.FusedAdamW (hot path) or any torch.optim optimizer.
     label_smoothing: the TRAINING loss is nn.CrossEntropyLoss(label_smoothing=...)'s; evaluation keeps the plain one.
     schedule: an object with step() (train.WarmupCosine), called after every optimizer step.
     history["grad_norm"] (the epoch mean of the pre-clip global gradient norm, summed on the device) is present
-    when the optimizer exposes `grad_norm` (train.FusedAdamW with max_grad_norm or skip_nonfinite)."""
+    when the optimizer exposes `grad_norm` (train.FusedAdamW with max_grad_norm or skip_nonfinite).
+    checkpoint: a path; train.save_checkpoint after every `checkpoint_every` epochs (and after the last one) with
+    extra = {"epoch": completed epochs, "history": ...} and the train loader's state (data.DeviceLoader: the
+    transform's generator and the shuffle epoch of datasets.batches).  Needs a train.FusedAdamW.
+    resume: with an existing `checkpoint` file, load it and continue from the stored epoch; the history is extended,
+    not restarted, and total_training_time covers this process only.  Under data parallelism rank 0 writes.
+    eval_ema: the validation pass runs inside optimizer.ema_weights() (train.FusedAdamW with ema_decay)."""
     dev = next(model.parameters()).device
     hist: Dict[str, List[float]] = {"train_loss": [], "train_acc": [], "val_loss": [], "val_acc": [], "epoch_time": []}
     track_norm = getattr(optimizer, "grad_norm", None) is not None
     if track_norm:
         hist["grad_norm"] = []
+    if checkpoint is not None and not isinstance(optimizer, T.FusedAdamW):
+        raise TypeError("fit: checkpoint= needs a train.FusedAdamW (its state is saved by parameter name)")
+    if checkpoint is not None and checkpoint_every < 1:
+        raise ValueError(f"fit: checkpoint_every must be >= 1, got {checkpoint_every}")
+    if eval_ema and getattr(optimizer, "ema_decay", None) is None:
+        raise ValueError("fit: eval_ema needs a train.FusedAdamW with ema_decay")
+    stateful = [train_loader] if hasattr(train_loader, "state_dict") else []
+    first_ep = 0
+    if resume and checkpoint is not None and os.path.exists(checkpoint):
+        extra = T.load_checkpoint(checkpoint, model, optimizer, schedule, stateful)
+        first_ep, hist = int(extra["epoch"]), {k: list(v) for k, v in extra["history"].items()}
+        log(f"Resumed {checkpoint} after epoch {first_ep}")
     t_start = time.perf_counter()
     peak_mb = 0.0
-    for ep in range(epochs):
+    for ep in range(first_ep, epochs):
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         model.train()
@@ -146,7 +166,11 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         if track_norm:
             hist["grad_norm"].append(norm_sum.item() / max(1, n_batches))
         if val_loader is not None:
-            ev = evaluate(model, val_loader)
+            if eval_ema:
+                with optimizer.ema_weights():
+                    ev = evaluate(model, val_loader)
+            else:
+                ev = evaluate(model, val_loader)
             hist["val_loss"].append(ev["test_loss"])
             hist["val_acc"].append(ev["test_acc"])
         torch.cuda.synchronize()
@@ -155,7 +179,9 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         log(f"Epoch {ep + 1}/{epochs} | Train Loss: {hist['train_loss'][-1]:.4f} | Train Acc: {hist['train_acc'][-1]:.2f}% | "
             + (f"Val Loss: {hist['val_loss'][-1]:.4f} | Val Acc: {hist['val_acc'][-1]:.2f}% | " if val_loader is not None else "")
             + f"Time: {hist['epoch_time'][-1]:.2f}s")
-    return {"history": hist, "avg_epoch_time": sum(hist["epoch_time"]) / max(1, epochs),
+        if checkpoint is not None and ((ep + 1) % checkpoint_every == 0 or ep + 1 == epochs):
+            T.save_checkpoint(checkpoint, model, optimizer, schedule, stateful, extra={"epoch": ep + 1, "history": hist})
+    return {"history": hist, "avg_epoch_time": sum(hist["epoch_time"]) / max(1, len(hist["epoch_time"])),
             "total_training_time": time.perf_counter() - t_start,
             "final_val_acc": hist["val_acc"][-1] if hist["val_acc"] else float("nan"),
             "final_val_loss": hist["val_loss"][-1] if hist["val_loss"] else float("nan"), "peak_gpu_memory_mb": peak_mb}

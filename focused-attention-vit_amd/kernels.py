@@ -871,20 +871,54 @@ def grad_norm(bufs, scale=1.0, max_norm=0.0, out=None, skipped=None, ws=None):
     return out
 
 
-def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None, coef=None, skip_nonfinite=False):
+def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None, coef=None, skip_nonfinite=False,
+          ema=None, ema_decay=0.0):
     """coef: one fp32 on the DEVICE (grad_norm's out[1:2]) the gradient is multiplied by when the kernel runs
-    (favit_adamw_clip); with skip_nonfinite a non-finite coefficient leaves p, m, v and p_lp untouched."""
+    (favit_adamw_clip); with skip_nonfinite a non-finite coefficient leaves p, m, v and p_lp untouched.
+    ema: a contiguous fp32 tensor of p's length that the same launch moves towards the updated parameters,
+    ema = ema_decay * ema + (1 - ema_decay) * p_new (favit_adamw_ema / favit_adamw_clip_ema); a skipped launch
+    leaves it untouched too.  None: the launches without the average."""
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
+    if ema is not None:
+        require_gpu(ema)
+        if ema.dtype != torch.float32 or ema.numel() != p.numel() or (ema.numel() and not ema.is_contiguous()):
+            raise TypeError("adamw: ema must be a contiguous fp32 tensor of p's length")
+        if not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"adamw: ema_decay must be in [0, 1], got {ema_decay}")
     if coef is None:
         if skip_nonfinite:
             raise ValueError("adamw: skip_nonfinite needs the device coefficient of grad_norm (coef)")
+        if ema is not None:
+            _abi.check(_abi.lib().favit_adamw_ema(_p(p), _p(g), _p(m), _p(v), _p(p_lp), _p(ema), p.numel(), lr, beta1,
+                                                  beta2, eps, wd, bc1, bc2, grad_scale, float(ema_decay), _st()),
+                       "favit_adamw_ema")
+            return
         _abi.check(_abi.lib().favit_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_lp), p.numel(), lr, beta1, beta2, eps, wd,
                                           bc1, bc2, grad_scale, _st()), "favit_adamw")
         return
     require_gpu(coef)
     if coef.dtype != torch.float32 or coef.numel() != 1:
         raise TypeError("adamw: coef must be one fp32 on the device")
+    if ema is not None:
+        _abi.check(_abi.lib().favit_adamw_clip_ema(_p(p), _p(g), _p(m), _p(v), _p(p_lp), _p(ema), p.numel(), lr, beta1,
+                                                   beta2, eps, wd, bc1, bc2, grad_scale, _p(coef),
+                                                   int(bool(skip_nonfinite)), float(ema_decay), _st()),
+                   "favit_adamw_clip_ema")
+        return
     _abi.check(_abi.lib().favit_adamw_clip(_p(p), _p(g), _p(m), _p(v), _p(p_lp), p.numel(), lr, beta1, beta2, eps, wd,
                                            bc1, bc2, grad_scale, _p(coef), int(bool(skip_nonfinite)), _st()),
                "favit_adamw_clip")
+
+
+def swap_params(a, b, a_lp=None):
+    """Exchange the contents of two flat fp32 tensors in place and, with a_lp, rewrite the bf16 mirror of `a` from
+    its new contents, in one pass (favit_swap_params).  No address changes."""
+    require_gpu(a, b, a_lp)
+    for t in (a, b):
+        if t.dtype != torch.float32 or (t.numel() and not t.is_contiguous()):
+            raise TypeError("swap_params: a and b must be contiguous fp32 tensors")
+    if a.numel() != b.numel() or (a_lp is not None and (a_lp.dtype != torch.bfloat16 or a_lp.numel() != a.numel()
+                                                         or (a_lp.numel() and not a_lp.is_contiguous()))):
+        raise TypeError("swap_params: b (fp32) and a_lp (bf16, optional) must have a's length")
+    _abi.check(_abi.lib().favit_swap_params(_p(a), _p(b), _p(a_lp), a.numel(), _st()), "favit_swap_params")

@@ -6,6 +6,9 @@ experiments/mhla_pretrained.py:308-327.  Loss and optimizer run in libfavit kern
 """
 from __future__ import annotations
 
+import contextlib
+import os
+import warnings
 from typing import Dict, List, Optional
 
 import torch
@@ -59,6 +62,27 @@ def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = N
     return [g for g in out if g["params"]]
 
 
+def ema_decay_at(decay: float, n: int, warmup: bool = False) -> float:
+    """The decay of the EMA update that follows n earlier ones: `decay`, or with warm-up min(decay, (1 + n) / (10 + n))
+    -- the average forgets its initial value (the untrained weights) quickly and reaches `decay` from below."""
+    return min(decay, (1 + n) / (10 + n)) if warmup else decay
+
+
+def _named_slots(opt: "FusedAdamW", model: torch.nn.Module):
+    """{state_dict key: (group index, offset, parameter)} of every parameter the optimizer holds in a flat buffer.
+    Raises ValueError for an optimizer parameter the model does not have (state is keyed by the model's names)."""
+    names = {id(t): k for k, t in model.state_dict(keep_vars=True).items()}
+    out = {}
+    for gi, g in enumerate(opt.groups):
+        for p_, o in zip(g["flat"].params, g["flat"].offsets):
+            k = names.get(id(p_))
+            if k is None:
+                raise ValueError(f"FusedAdamW: a parameter of shape {tuple(p_.shape)} in group {gi} does not belong to "
+                                 f"the model whose names key the optimizer state")
+            out[k] = (gi, o, p_)
+    return out
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics; one favit_adamw launch per parameter group over flat
     parameter / gradient / moment buffers (and the DP all-reduce runs on the same flat
@@ -74,10 +98,23 @@ class FusedAdamW:
     skip): the next applied update uses bias-correction factors one step further on, which after the first few
     steps is a difference far below the update's own rounding.
     Read-outs (None when both options are off): `grad_norm`, a 0-dim fp32 device view of the last step's pre-clip
-    norm, and `skipped_steps`, a 0-dim int32 device view.  Both options need at most 16 parameter groups."""
+    norm, and `skipped_steps`, a 0-dim int32 device view.  Both options need at most 16 parameter groups.
+
+    ema_decay (in [0, 1), None = off): every group keeps `g["ema"]`, an fp32 flat buffer laid out like flat_p and
+    initialised as a copy of it, and the group's AdamW launch itself moves it towards the parameters it has just
+    computed, ema = d * ema + (1 - d) * p (favit_adamw_ema / favit_adamw_clip_ema): no extra launch, no second pass
+    over the parameters.  d = ema_decay_at(ema_decay, ema_updates, ema_warmup), a by-value argument of the launch;
+    `ema_updates` counts the EMA updates issued so far.  On a device-side skipped step `ema_updates` still advances,
+    like the step count (the launch leaves the average itself untouched).  Frozen parameters are in no flat buffer and
+    are their own average.  `ema_weights()` evaluates with the average, `ema_state_dict(model)` exports it.  Under data
+    parallelism every rank's average is bitwise the same (same p, same decay).
+
+    state_dict(model) / load_state_dict(state, model): m, v and the average per parameter, keyed by the model's
+    state_dict names (independent of the flat layout), the hyper-parameters per group and the counters."""
 
     def __init__(self, groups, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, bucket_mb=None,
-                 distributed=None, wire_dtype=None, max_grad_norm=None, skip_nonfinite=False):
+                 distributed=None, wire_dtype=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                 ema_warmup=False):
         if isinstance(groups, torch.nn.Module):
             groups = [{"params": list(groups.parameters())}]
         elif groups and not isinstance(groups[0], dict):
@@ -87,6 +124,12 @@ class FusedAdamW:
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         self._guard = self.max_grad_norm is not None or self.skip_nonfinite
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay must be in [0, 1) (or None for no average), got {ema_decay}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_updates = 0
+        self._ema_swapped = False
         if self._guard and len(groups) > K.GRAD_NORM_MAX_BUFS:
             raise ValueError(f"FusedAdamW: max_grad_norm / skip_nonfinite take at most {K.GRAD_NORM_MAX_BUFS} parameter "
                              f"groups, got {len(groups)}")
@@ -105,6 +148,11 @@ class FusedAdamW:
             if self.groups[-1]["lp"] is not None:
                 K.cast(flat.flat_p, torch.bfloat16, out=self.groups[-1]["lp"])
                 self.groups[-1]["mirror"] = F.register_lp_mirror(flat.flat_p, self.groups[-1]["lp"], flat.params)
+            if self.ema_decay is not None:
+                if not flat.flat_p.is_cuda:
+                    raise RuntimeError("FusedAdamW: ema_decay runs in HIP kernels; the parameters are on the CPU (there "
+                                       "is no CPU fallback)")
+                self.groups[-1]["ema"] = flat.flat_p.clone()         # allocated here: step() allocates nothing
         self.steps = 0
         self.world = torch.distributed.get_world_size() if dist_on else 1
         # norm / coefficient, skip counter and the norm kernel's workspace live as long as the optimizer: step()
@@ -153,7 +201,14 @@ class FusedAdamW:
                 g["mirror"].refresh_if_stale()
 
     def step(self):
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.step() inside ema_weights(): the parameters hold the average")
         self.steps += 1
+        ema_kw = [{} for _ in self.groups]                 # (no average: exactly the launches without one)
+        if self.ema_decay is not None:
+            d = ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)
+            self.ema_updates += 1
+            ema_kw = [{"ema": g["ema"], "ema_decay": d} for g in self.groups]
         if self._guard:
             for g in self.groups:                      # the norm is that of the COMPLETE all-reduced gradient
                 if g["sync"] is not None:
@@ -161,22 +216,135 @@ class FusedAdamW:
             K.grad_norm([g["flat"].flat_g for g in self.groups], scale=1.0 / self.world,
                         max_norm=self.max_grad_norm or 0.0, out=self._norm_out, skipped=self._skipped, ws=self._norm_ws)
             coef = self._norm_out[1:2]
-            for g in self.groups:
+            for g, kw in zip(self.groups, ema_kw):
                 f = g["flat"]
                 K.adamw(f.flat_p, f.flat_g, g["m"], g["v"], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
                         g["weight_decay"], self.steps, grad_scale=1.0 / self.world, p_lp=g["lp"], coef=coef,
-                        skip_nonfinite=self.skip_nonfinite)
+                        skip_nonfinite=self.skip_nonfinite, **kw)
             # (a skipped launch left parameters and mirrors as they were: still a matching pair)
             F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
             return
-        for g in self.groups:
+        for g, kw in zip(self.groups, ema_kw):
             if g["sync"] is not None:
                 g["sync"].finish(average=False)
             f = g["flat"]
             K.adamw(f.flat_p, f.flat_g, g["m"], g["v"], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                    g["weight_decay"], self.steps, grad_scale=1.0 / self.world, p_lp=g["lp"])
+                    g["weight_decay"], self.steps, grad_scale=1.0 / self.world, p_lp=g["lp"], **kw)
         # the AdamW kernel rewrote the bf16 mirrors itself: they stay valid across the epoch bump
         F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
+
+    # ---- averaged weights ----
+    def _swap_ema(self):
+        for g in self.groups:
+            K.swap_params(g["flat"].flat_p, g["ema"], g["lp"])
+        # as after step(): the parameters changed through raw pointers, the mirrors were rewritten with them
+        F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with opt.ema_weights(): evaluate(model)``: inside, the trainable parameters (and their bf16 mirrors) hold
+        the average and `g["ema"]` holds the training weights; one favit_swap_params launch per group on entry and
+        on exit (also when the body raises), no address changes -- a captured GraphedStep stays valid.  Frozen
+        parameters are untouched.  Nesting and step() inside the context raise RuntimeError."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_weights(): the optimizer keeps no average (ema_decay=None)")
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.ema_weights() does not nest")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
+    def ema_state_dict(self, model: torch.nn.Module) -> Dict[str, torch.Tensor]:
+        """model.state_dict() with the average in place of every trainable parameter (copies; current values for
+        frozen parameters and buffers): loadable by model.load_state_dict and by the reference's modules."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_state_dict(): the optimizer keeps no average (ema_decay=None)")
+        slots = _named_slots(self, model)
+        out = {}
+        for k, t in model.state_dict().items():
+            if k in slots:
+                gi, o, p_ = slots[k]
+                g = self.groups[gi]
+                src = g["flat"].flat_p if self._ema_swapped else g["ema"]
+                out[k] = src[o:o + p_.numel()].view(p_.shape).clone()
+            else:
+                out[k] = t.detach().clone()
+        return out
+
+    # ---- checkpoint state ----
+    def state_dict(self, model: torch.nn.Module) -> Dict:
+        """Plain containers and CPU tensors only.  `model` supplies the names (its state_dict keys)."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.state_dict() inside ema_weights(): the buffers are exchanged")
+        slots = _named_slots(self, model)
+        state = {}
+        for k, (gi, o, p_) in slots.items():
+            g = self.groups[gi]
+            cut = lambda t: t[o:o + p_.numel()].view(p_.shape).detach().cpu().clone()
+            state[k] = {"m": cut(g["m"]), "v": cut(g["v"])}
+            if self.ema_decay is not None:
+                state[k]["ema"] = cut(g["ema"])
+        groups = [{"lr": float(g["lr"]), "betas": [float(b) for b in g["betas"]], "eps": float(g["eps"]),
+                   "weight_decay": float(g["weight_decay"]), "names": [k for k, s_ in slots.items() if s_[0] == gi]}
+                  for gi, g in enumerate(self.groups)]
+        return {"steps": int(self.steps), "ema_updates": int(self.ema_updates),
+                "skipped_steps": None if self.skipped_steps is None else int(self.skipped_steps),
+                "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite,
+                "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup, "groups": groups, "state": state}
+
+    def check_state_dict(self, state: Dict, model: torch.nn.Module):
+        """Everything load_state_dict needs to hold, checked without writing: group membership, shapes, and that
+        the file has an average if this optimizer keeps one.  ValueError names the offending key."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.load_state_dict() inside ema_weights(): the buffers are exchanged")
+        slots = _named_slots(self, model)
+        for k in ("steps", "ema_updates", "groups", "state"):
+            if k not in state:
+                raise ValueError(f"optimizer state: entry '{k}' is missing")
+        if len(state["groups"]) != len(self.groups):
+            raise ValueError(f"optimizer state: 'groups' has {len(state['groups'])} groups, the optimizer {len(self.groups)}")
+        where = {k: gi for gi, g in enumerate(state["groups"]) for k in g["names"]}
+        for k, (gi, o, p_) in slots.items():
+            if k not in where:
+                raise ValueError(f"optimizer state: parameter '{k}' is missing")
+            if where[k] != gi:
+                raise ValueError(f"optimizer state: parameter '{k}' is in group {where[k]} of the file and in group {gi} "
+                                 f"of the optimizer")
+            st = state["state"].get(k)
+            if st is None:
+                raise ValueError(f"optimizer state: no state for parameter '{k}'")
+            for key in ("m", "v") + (("ema",) if self.ema_decay is not None else ()):
+                if key not in st:
+                    raise ValueError(f"optimizer state: parameter '{k}' has no '{key}'"
+                                     + (" (the optimizer keeps an average, the file does not)" if key == "ema" else ""))
+                if tuple(st[key].shape) != tuple(p_.shape):
+                    raise ValueError(f"optimizer state: '{key}' of parameter '{k}' has shape {tuple(st[key].shape)}, the "
+                                     f"parameter {tuple(p_.shape)}")
+        for k in where:
+            if k not in slots:
+                raise ValueError(f"optimizer state: parameter '{k}' is not held by the optimizer")
+        return slots
+
+    def load_state_dict(self, state: Dict, model: torch.nn.Module) -> None:
+        """Restores m, v, the average (copied into their flat slices by offset), the counters and the groups' lr, betas,
+        eps and weight_decay.  max_grad_norm, skip_nonfinite, ema_decay and ema_warmup stay as constructed (they decide
+        which buffers exist); a file with an average loaded into an optimizer without one drops it."""
+        slots = self.check_state_dict(state, model)
+        with torch.no_grad():
+            for k, (gi, o, p_) in slots.items():
+                g, st = self.groups[gi], state["state"][k]
+                for key in ("m", "v") + (("ema",) if self.ema_decay is not None else ()):
+                    g[key][o:o + p_.numel()].copy_(st[key].reshape(-1))
+            if self.skipped_steps is not None:
+                self._skipped.fill_(int(state.get("skipped_steps") or 0))
+        for g, sg in zip(self.groups, state["groups"]):
+            g["lr"], g["betas"] = float(sg["lr"]), (float(sg["betas"][0]), float(sg["betas"][1]))
+            g["eps"], g["weight_decay"] = float(sg["eps"]), float(sg["weight_decay"])
+        self.steps, self.ema_updates = int(state["steps"]), int(state["ema_updates"])
 
 
 class WarmupCosine:
@@ -222,6 +390,26 @@ class WarmupCosine:
     @property
     def last_lr(self):
         return [g["lr"] for g in self._groups]
+
+    def state_dict(self) -> Dict:
+        return {"t": int(self.t), "base_lrs": [float(b) for b in self.base_lrs], "warmup_steps": self.warmup_steps,
+                "total_steps": self.total_steps, "min_ratio": self.min_ratio}
+
+    def check_state_dict(self, state: Dict) -> None:
+        for k in ("t", "base_lrs", "warmup_steps", "total_steps", "min_ratio"):
+            if k not in state:
+                raise ValueError(f"schedule state: entry '{k}' is missing")
+        if len(state["base_lrs"]) != len(self._groups):
+            raise ValueError(f"schedule state: 'base_lrs' has {len(state['base_lrs'])} entries, the optimizer "
+                             f"{len(self._groups)} groups")
+
+    def load_state_dict(self, state: Dict) -> None:
+        """Restores the position and the base rates and re-applies the rates of step t to the optimizer's groups."""
+        self.check_state_dict(state)
+        self.t, self.base_lrs = int(state["t"]), [float(b) for b in state["base_lrs"]]
+        self.warmup_steps, self.total_steps = int(state["warmup_steps"]), int(state["total_steps"])
+        self.min_ratio = float(state["min_ratio"])
+        self._apply()
 
 
 class Health:
@@ -274,6 +462,131 @@ class Health:
         if found:
             out["tensors"] = found
         return out or None
+
+
+CHECKPOINT_FORMAT, CHECKPOINT_VERSION = "favit-train-state", 1
+
+
+def save_checkpoint(path: str, model: torch.nn.Module, opt: Optional[FusedAdamW] = None, schedule=None, loaders=(),
+                    extra=None) -> None:
+    """Everything a run needs to continue, in one torch.save of plain containers (dict / list / str / int / float /
+    None) and CPU tensors -- no pickled class, so ``torch.load(path, map_location="cpu", weights_only=True)`` reads it.
+    Written to ``path + ".tmp"`` and moved into place with os.replace: an interrupted save leaves the previous file.
+
+        format "favit-train-state", version 1
+        compute_mode   functional.get_compute_mode() at the save
+        model          model.state_dict(), fp32; the reference's keys, loadable by either side's modules
+        optimizer      FusedAdamW.state_dict(model): m / v / ema per parameter NAME, group hyper-parameters, counters
+        schedule       WarmupCosine.state_dict()
+        loaders        [x.state_dict() for x in loaders]  (data.DeviceLoader, data.DeviceTransform, datasets.batches(...))
+        rng            {"torch_cpu": torch.get_rng_state(), "dropout_epoch": the registered epoch word's value or None}
+        extra          the caller's (harness.fit: completed epochs and the history)
+
+    Not saved: the fp8 delayed-scaling histories (functional._FP8_HIST).  After a resume in fp8 mode every site
+    measures afresh, as on a run's first step.  Reading the skip counter and the dropout epoch is a host sync.
+    Under data parallelism every rank holds the same state (parameters, moments and the average are bitwise equal
+    across ranks), and only rank 0 writes; the other ranks return at once."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
+        return
+    word = F.get_dropout_epoch()
+    obj = {
+        "format": CHECKPOINT_FORMAT, "version": CHECKPOINT_VERSION, "compute_mode": F.get_compute_mode(),
+        "model": {k: (v.detach().to("cpu", torch.float32) if v.is_floating_point() else v.detach().cpu()).clone()
+                  for k, v in model.state_dict().items()},
+        "optimizer": None if opt is None else opt.state_dict(model),
+        "schedule": None if schedule is None else schedule.state_dict(),
+        "loaders": [x.state_dict() for x in loaders],
+        "rng": {"torch_cpu": torch.get_rng_state().clone(), "dropout_epoch": None if word is None else int(word.item())},
+        "extra": extra,
+    }
+    tmp = path + ".tmp"
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def load_checkpoint(path: str, model: torch.nn.Module, opt: Optional[FusedAdamW] = None, schedule=None, loaders=(),
+                    use_ema: bool = False):
+    """Restore what save_checkpoint wrote into existing objects; returns the file's `extra`.
+
+    Everything is validated before anything is written: format and version, the model's keys and shapes, the
+    optimizer's group membership and shapes (and that the file holds an average if `opt` keeps one), the schedule
+    and the loader states.  A mismatch raises ValueError naming the key and leaves model and optimizer untouched.
+    Then: model.load_state_dict (an in-place copy into the flat-buffer views; the bf16 mirrors see the version
+    counters), m / v / ema into their flat slices, the torch CPU generator (the source of the dropout seeds), and the
+    dropout epoch word -- written IN PLACE when one is registered (a captured GraphedStep holds its address),
+    registered when the file has one and the process none.
+    use_ema=True (with opt=None): the averaged weights go into the model, for evaluation or export.
+    A compute mode other than the file's is a warning.  The fp8 delayed-scaling histories are not part of the file:
+    after a resume in fp8 mode every site measures afresh."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or ck.get("format") != CHECKPOINT_FORMAT:
+        raise ValueError(f"{path}: 'format' is {ck.get('format') if isinstance(ck, dict) else type(ck).__name__!r}, "
+                         f"expected {CHECKPOINT_FORMAT!r}")
+    if ck.get("version") != CHECKPOINT_VERSION:
+        raise ValueError(f"{path}: 'version' {ck.get('version')!r} is not supported (this code reads version "
+                         f"{CHECKPOINT_VERSION})")
+    weights = dict(ck["model"])
+    if use_ema:
+        if opt is not None:
+            raise ValueError("load_checkpoint: use_ema loads the average INTO the model and takes no optimizer (with one, "
+                             "load normally and use opt.ema_weights())")
+        ost = ck.get("optimizer")
+        if ost is None or ost.get("ema_decay") is None:
+            raise ValueError(f"{path}: 'optimizer' holds no average (use_ema=True)")
+        for k, st in ost["state"].items():
+            if "ema" not in st:
+                raise ValueError(f"{path}: parameter '{k}' has no 'ema' (use_ema=True)")
+            weights[k] = st["ema"]
+    own = model.state_dict()
+    for k in own:
+        if k not in weights:
+            raise ValueError(f"{path}: model key '{k}' is missing from the file")
+    for k, v in weights.items():
+        if k not in own:
+            raise ValueError(f"{path}: the file's model key '{k}' does not exist in the model")
+        if tuple(v.shape) != tuple(own[k].shape):
+            raise ValueError(f"{path}: model key '{k}' has shape {tuple(v.shape)} in the file, {tuple(own[k].shape)} in "
+                             f"the model")
+    if opt is not None:
+        if ck.get("optimizer") is None:
+            raise ValueError(f"{path}: 'optimizer' is missing from the file")
+        opt.check_state_dict(ck["optimizer"], model)
+    if schedule is not None:
+        if ck.get("schedule") is None:
+            raise ValueError(f"{path}: 'schedule' is missing from the file")
+        schedule.check_state_dict(ck["schedule"])
+    loaders = list(loaders)
+    if loaders and len(ck.get("loaders") or []) != len(loaders):
+        raise ValueError(f"{path}: 'loaders' has {len(ck.get('loaders') or [])} entries, {len(loaders)} objects were given")
+    for x, st in zip(loaders, ck.get("loaders") or []):
+        if hasattr(x, "check_state_dict"):
+            x.check_state_dict(st)
+    if ck.get("compute_mode") != F.get_compute_mode():
+        warnings.warn(f"{path} was written in compute mode {ck.get('compute_mode')!r}, the process runs "
+                      f"{F.get_compute_mode()!r}")
+    # ---- nothing was written above this line ----
+    model.load_state_dict(weights)
+    if opt is not None:
+        opt.load_state_dict(ck["optimizer"], model)
+    if schedule is not None:
+        schedule.load_state_dict(ck["schedule"])
+    for x, st in zip(loaders, ck.get("loaders") or []):
+        x.load_state_dict(st)
+    rng = ck.get("rng") or {}
+    if rng.get("torch_cpu") is not None:
+        torch.set_rng_state(rng["torch_cpu"])
+    if rng.get("dropout_epoch") is not None:
+        word = F.get_dropout_epoch()
+        dev = next(model.parameters()).device
+        if word is not None:
+            word.fill_(int(rng["dropout_epoch"]))
+        elif dev.type == "cuda":
+            F.set_dropout_epoch(torch.full((1,), int(rng["dropout_epoch"]), dtype=torch.int64, device=dev))
+    return ck.get("extra")
 
 
 def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0):

@@ -504,6 +504,27 @@ int favit_adamw_clip(float* p, const float* g, float* m, float* v, void* p_bf16,
                      float beta2, float eps, float weight_decay, float bias_c1, float bias_c2, float grad_scale,
                      const float* coef, int32_t skip_nonfinite, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Averaged weights (additive in ABI 8): an exponential moving average of the parameters kept by the AdamW launch
+ * itself, and the exchange that puts it in the parameters' place for evaluation.
+ * ---------------------------------------------------------------------------------- */
+/* favit_adamw / favit_adamw_clip, and in the same pass, with p_new the parameter this launch writes,
+ *   ema[i] = fmaf(ema_decay, ema[i], (1 - ema_decay) * p_new[i])       0 <= ema_decay <= 1 (else FAVIT_ERR_INVALID)
+ * ema: [n] fp32 on the device, 4-byte aligned, not overlapping p.  p, m, v and p_bf16 get exactly the bits of the
+ * entry point without the average.  ema_decay == 0 copies p_new (for finite ema).  A launch skipped by
+ * skip_nonfinite leaves ema untouched like everything else.  38 bytes of traffic per element instead of 30. */
+int favit_adamw_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, int64_t n, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, float bias_c1, float bias_c2,
+                    float grad_scale, float ema_decay, void* stream);
+int favit_adamw_clip_ema(float* p, const float* g, float* m, float* v, void* p_bf16, float* ema, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, float bias_c1, float bias_c2,
+                         float grad_scale, const float* coef, int32_t skip_nonfinite, float ema_decay, void* stream);
+
+/* Exchange two flat fp32 buffers of n elements in one pass: a[i], b[i] = b[i], a[i]; with a_bf16 != NULL also
+ * a_bf16[i] = bf16(new a[i]) (the compute-dtype mirror of a).  a and b must not overlap (a == b is refused).  No
+ * address changes, so a captured graph that reads a / a_bf16 stays valid; two calls restore every bit. */
+int favit_swap_params(float* a, float* b, void* a_bf16, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

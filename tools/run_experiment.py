@@ -163,6 +163,16 @@ def parse_args(argv=None):
     ap.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine"],
                     help="cosine: linear warm-up over --warmup_epochs, then half a cosine to zero over the remaining epochs")
     ap.add_argument("--warmup_epochs", type=float, default=0.0, help="--lr_schedule cosine: length of the linear warm-up")
+    ap.add_argument("--ema_decay", type=float, default=None,
+                    help="keep an exponential moving average of the trainable weights with this decay, inside the AdamW "
+                         "launch (default: none)")
+    ap.add_argument("--ema_warmup", action="store_true", help="--ema_decay: decay min(d, (1 + n) / (10 + n)) at update n")
+    ap.add_argument("--eval_ema", action="store_true", help="--ema_decay: validate and test with the averaged weights")
+    ap.add_argument("--checkpoint", default=None, metavar="PATH",
+                    help="write the resumable training state here (train.save_checkpoint) and, at the end, the model-only "
+                         "file PATH.ema with the averaged weights (the plain weights without --ema_decay)")
+    ap.add_argument("--checkpoint_every", type=int, default=1, metavar="N", help="--checkpoint: every N epochs")
+    ap.add_argument("--resume", action="store_true", help="--checkpoint: continue from PATH if it exists")
     ap.add_argument("--bucket_tokens", action="store_true",
                     help="sppp_mhla: run batches that mix images with num_superpixels and num_superpixels - 1 tokens group by "
                          "group (models.sppp.TokenBucketed; the reference -- and this tool without the flag -- fails on "
@@ -214,7 +224,12 @@ def main(argv=None):
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
     opt = pkg.train.FusedAdamW(pkg.train.param_groups(model, lr=a.learning_rate, head_lr=a.head_learning_rate),
                                lr=a.learning_rate, weight_decay=a.weight_decay, distributed=False,
-                               max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite)
+                               max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay,
+                               ema_warmup=a.ema_warmup)
+    if a.eval_ema and a.ema_decay is None:
+        raise SystemExit("--eval_ema needs --ema_decay")
+    if (a.resume or a.checkpoint_every != 1) and a.checkpoint is None:
+        raise SystemExit("--resume / --checkpoint_every need --checkpoint")
 
     class Epochs:            # a fresh shuffle per epoch
         def __init__(self, x, y, shuffle):
@@ -239,8 +254,21 @@ def main(argv=None):
         schedule = pkg.train.WarmupCosine(opt, int(round(a.warmup_epochs * per_epoch)), max(1, a.epochs * per_epoch))
     with torch.cuda.stream(work):
         res = pkg.harness.fit(run, train_loader, test_loader, opt, a.epochs, label_smoothing=a.label_smoothing,
-                              schedule=schedule)
-        ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
+                              schedule=schedule, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
+                              resume=a.resume, eval_ema=a.eval_ema)
+        if a.eval_ema:
+            with opt.ema_weights():
+                ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
+        else:
+            ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
+        if a.checkpoint is not None:
+            # the model a user takes away: the averaged weights when there is an average, in a model-only file
+            if a.ema_decay is not None:
+                with opt.ema_weights():
+                    pkg.train.save_checkpoint(a.checkpoint + ".ema", model)
+            else:
+                pkg.train.save_checkpoint(a.checkpoint + ".ema", model)
+            print(f"Model weights saved to {a.checkpoint}.ema")
     torch.cuda.current_stream().wait_stream(work)
     row = {"model": a.experiment, "img_size": a.img_size, "patch_size": a.patch_size, "embed_dim": a.embed_dim, "depth": a.depth,
            "num_heads": a.num_heads, "window_size": a.window_size, "total_parameters": sum(p.numel() for p in model.parameters()),
