@@ -118,6 +118,8 @@ _SIGS = {
     "favit_adamw_clip_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, f32, vp],
                              C.c_int),
     "favit_swap_params": ([vp, vp, vp, i64, vp], C.c_int),
+    "favit_batch_mix": ([vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
+    "favit_cross_entropy_mix": ([vp, vp, vp, vp, vp, i32, i32, f32, f32, vp], C.c_int),
 }
 
 _lib = None

@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Dict, Iterable, Iterator, Optional, Sequence, Tuple
+from typing import Dict, Iterable, Iterator, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -291,14 +291,136 @@ def get_transforms(dataset_name: str, img_size: int = 224, seed: int = 0) -> Dic
             "test": DeviceTransform("resize", img_size, half, half, seed)}
 
 
+class MixedLabels(NamedTuple):
+    """The labels of a batch mixed by BatchMix: row b's target is lam[b] * onehot(labels[b]) + (1 - lam[b]) *
+    onehot(labels[B-1-b]) (train.cross_entropy(..., mix_lam=lam)).  labels: int64 [B], lam: fp32 [B], on the device."""
+    labels: torch.Tensor
+    lam: torch.Tensor
+
+
+class BatchMix:
+    """Mixup / CutMix of a device batch with its own flip (timm's Mixup): row b is paired with row B-1-b, the images
+    are mixed in place by one kernel (favit_batch_mix) and the labels become MixedLabels.
+
+    Per draw -- one for the whole batch (mode 'batch') or one per row ('elem'):
+      with probability `prob` the row is mixed, otherwise left alone (lam = 1);
+      CutMix is chosen with probability `switch_prob` when both alphas are > 0, else whichever alpha is > 0 is used;
+      lam ~ Beta(alpha, alpha);  CutMix: r = sqrt(1 - lam), a box of int(S r) x int(S r) pixels around a uniform centre,
+      clipped to the image, and lam = 1 - box_area / S^2 (an empty box leaves the row alone).
+    The middle row of an odd batch is its own partner and is always left alone.  The draws come from a numpy generator
+    owned by the object (as DeviceTransform's do) and are part of the checkpoint state."""
+
+    def __init__(self, mixup_alpha: float = 0.8, cutmix_alpha: float = 1.0, prob: float = 1.0,
+                 switch_prob: float = 0.5, mode: str = "batch", seed: int = 0):
+        if not (mixup_alpha >= 0.0 and cutmix_alpha >= 0.0):
+            raise ValueError(f"BatchMix: alphas must be >= 0, got {mixup_alpha}, {cutmix_alpha}")
+        if mixup_alpha == 0.0 and cutmix_alpha == 0.0:
+            raise ValueError("BatchMix: mixup_alpha and cutmix_alpha are both 0 (nothing to mix)")
+        if not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+            raise ValueError(f"BatchMix: prob and switch_prob must be in [0, 1], got {prob}, {switch_prob}")
+        if mode not in ("batch", "elem"):
+            raise ValueError(f"BatchMix: unknown mode {mode!r} ('batch' or 'elem')")
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob, self.mode = float(prob), float(switch_prob), mode
+        self.rng = np.random.RandomState(seed)
+
+    # ---- checkpoint state: the generator of the draws (the form of DeviceTransform's) ----
+    def state_dict(self) -> Dict:
+        name, keys, pos, has_gauss, cached = self.rng.get_state()
+        return {"mode": self.mode, "bit_generator": str(name), "keys": torch.from_numpy(keys.astype(np.int64)),
+                "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+    def check_state_dict(self, state: Dict) -> None:
+        for k in ("bit_generator", "keys", "pos", "has_gauss", "cached_gaussian"):
+            if k not in state:
+                raise ValueError(f"BatchMix state: entry '{k}' is missing")
+        if state["bit_generator"] != "MT19937" or tuple(state["keys"].shape) != (624,):
+            raise ValueError("BatchMix state: 'keys' is not the 624-word state of an MT19937 generator")
+        if state.get("mode", self.mode) != self.mode:
+            raise ValueError(f"BatchMix state: 'mode' is {state['mode']!r}, the mix is {self.mode!r}")
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.check_state_dict(state)
+        self.rng.set_state(("MT19937", state["keys"].numpy().astype(np.uint32), int(state["pos"]),
+                            int(state["has_gauss"]), float(state["cached_gaussian"])))
+
+    def _draw(self, S: int):
+        """One draw: (lam, (y0, y1, x0, x1)); lam = 1 and a zero box mean 'leave the row alone'."""
+        rng = self.rng
+        if not rng.rand() < self.prob:
+            return 1.0, (0, 0, 0, 0)
+        if self.mixup_alpha > 0.0 and self.cutmix_alpha > 0.0:
+            cut = bool(rng.rand() < self.switch_prob)
+        else:
+            cut = self.cutmix_alpha > 0.0
+        alpha = self.cutmix_alpha if cut else self.mixup_alpha
+        lam = float(rng.beta(alpha, alpha))
+        if not cut:
+            return lam, (0, 0, 0, 0)
+        r = math.sqrt(1.0 - lam)
+        ch, cw = int(S * r), int(S * r)
+        cy, cx = int(rng.randint(S)), int(rng.randint(S))
+        y0, y1 = min(max(cy - ch // 2, 0), S), min(max(cy + ch // 2, 0), S)
+        x0, x1 = min(max(cx - cw // 2, 0), S), min(max(cx + cw // 2, 0), S)
+        area = (y1 - y0) * (x1 - x0)
+        if area == 0:
+            return 1.0, (0, 0, 0, 0)
+        return 1.0 - area / float(S * S), (y0, y1, x0, x1)
+
+    def params(self, B: int, S: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Host parameters of one batch of B images of S x S pixels: (lam [B] fp32, box [B, 4] int32 = y0, y1, x0, x1)."""
+        B, S = int(B), int(S)
+        if B < 1 or S < 1:
+            raise ValueError(f"BatchMix.params: B and S must be positive, got {B}, {S}")
+        lam = np.ones(B, dtype=np.float32)
+        box = np.zeros((B, 4), dtype=np.int32)
+        if self.mode == "batch":
+            lam[:], box[:] = self._draw(S)
+        else:
+            for b in range(B):
+                lam[b], box[b] = self._draw(S)
+        if B % 2:
+            lam[B // 2], box[B // 2] = 1.0, 0
+        return lam, box
+
+    @staticmethod
+    def check_params(lam: np.ndarray, box: np.ndarray, B: int) -> None:
+        if lam.shape != (B,) or box.shape != (B, 4):
+            raise ValueError(f"BatchMix: params must be (lam [{B}], box [{B}, 4])")
+        if not (np.all(lam >= 0.0) and np.all(lam <= 1.0)):
+            raise ValueError("BatchMix: every lam must lie in [0, 1]")
+
+    def __call__(self, images: torch.Tensor, labels: torch.Tensor, params=None):
+        """images: fp32 [B, C, S, S] on the GPU, mixed IN PLACE; labels: int64 [B].  params: (lam, box) as params()
+        returns them, instead of a fresh draw.  Returns (images, MixedLabels(labels, lam on the device))."""
+        K.require_gpu(images, labels)
+        if images.dim() != 4 or images.shape[2] != images.shape[3]:
+            raise TypeError("BatchMix expects a [B, C, S, S] batch of square images")
+        B, S = images.shape[0], images.shape[3]
+        if tuple(labels.shape) != (B,):
+            raise TypeError(f"BatchMix: labels must be [{B}]")
+        lam, box = self.params(B, S) if params is None else params
+        lam = np.ascontiguousarray(lam, dtype=np.float32)
+        box = np.ascontiguousarray(box, dtype=np.int32)
+        self.check_params(lam, box, B)
+        d_lam = torch.from_numpy(lam).to(images.device, non_blocking=True)
+        d_box = torch.from_numpy(box).to(images.device, non_blocking=True)
+        K.batch_mix(images, d_lam, d_box)
+        return images, MixedLabels(labels, d_lam)
+
+
 class DeviceLoader:
     """Iterates (images fp32 [B,C,S,S], labels int64 [B]) on the GPU from an iterable of HOST batches
     (uint8 [B,H,W,C] array / tensor, or a RaggedBatch of mixed-size images; integer labels).  Batch k+1 is copied (pinned staging buffers, a dedicated
     copy stream) and transformed while the consumer computes on batch k: no host-side blocking .to(device)."""
 
     def __init__(self, host_batches: Iterable, transform: DeviceTransform, device: Optional[torch.device] = None,
-                 segmenter=None):
-        """segmenter (optional): a models.sppp.SuperpixelSegmentation (``model.segmentation`` of the SPPP models).  The
+                 segmenter=None, mix: Optional[BatchMix] = None):
+        """mix (optional): a BatchMix, applied to every batch directly after the transform (with a segmenter: before
+        the segmentation, which therefore sees the image the model sees).  The loader then yields
+        (images, MixedLabels(labels, lam)) and its state carries the mix's generator under "mix".
+
+        segmenter (optional): a models.sppp.SuperpixelSegmentation (``model.segmentation`` of the SPPP models).  The
         label maps of batch k+1 are then computed by the device SLIC on the loader's preparation stream while the
         consumer trains on batch k, and installed (``set_label_maps``) when the batch is yielded -- the reference
         segments inside forward (models/sppp_mhla.py:278), on the critical path of every step.
@@ -311,7 +433,7 @@ class DeviceLoader:
         self.src, self.tf = host_batches, transform
         self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.copy_stream = torch.cuda.Stream(device=self.dev)
-        self.segmenter = segmenter
+        self.segmenter, self.mix = segmenter, mix
         # the segmentation stream is confined to SEGMENTER_CUS compute units (streams.py): its grids would otherwise
         # fill every CU and the consumer's short launches would queue behind them
         self.prep_stream = streams.cu_masked_stream(SEGMENTER_CUS, self.dev) if segmenter is not None else None
@@ -324,20 +446,31 @@ class DeviceLoader:
 
     # ---- checkpoint state, between epochs: the transform's generator and the source's shuffle epoch ----
     def state_dict(self) -> Dict:
-        return {"transform": self.tf.state_dict(),
-                "batches": self.src.state_dict() if hasattr(self.src, "state_dict") else None}
+        state = {"transform": self.tf.state_dict(),
+                 "batches": self.src.state_dict() if hasattr(self.src, "state_dict") else None}
+        if self.mix is not None:
+            state["mix"] = self.mix.state_dict()
+        return state
 
     def check_state_dict(self, state: Dict) -> None:
         for k in ("transform", "batches"):
             if k not in state:
                 raise ValueError(f"DeviceLoader state: entry '{k}' is missing")
+        if ("mix" in state) != (self.mix is not None):
+            raise ValueError("DeviceLoader state: it was saved " + ("with" if "mix" in state else "without") +
+                             " a batch mix and this loader is built " + ("without" if "mix" in state else "with") +
+                             " one")
         self.tf.check_state_dict(state["transform"])
+        if self.mix is not None:
+            self.mix.check_state_dict(state["mix"])
         if state["batches"] is not None and hasattr(self.src, "check_state_dict"):
             self.src.check_state_dict(state["batches"])
 
     def load_state_dict(self, state: Dict) -> None:
         self.check_state_dict(state)
         self.tf.load_state_dict(state["transform"])
+        if self.mix is not None:
+            self.mix.load_state_dict(state["mix"])
         if state["batches"] is not None and hasattr(self.src, "load_state_dict"):
             self.src.load_state_dict(state["batches"])
 
@@ -393,6 +526,8 @@ class DeviceLoader:
             with torch.cuda.stream(self.prep_stream):
                 self.prep_stream.wait_event(ev)
                 x = self.tf(d_img)
+                if self.mix is not None:
+                    x, d_lab = self.mix(x, d_lab)
                 maps = self.segmenter.segment_device(x)
                 derived = self.segmenter.derive_for(maps)        # patch mapping + centroids: functions of the maps alone
                 d_img.record_stream(self.prep_stream)
@@ -420,7 +555,8 @@ class DeviceLoader:
         d_img, d_lab, ev = staged
         cs = torch.cuda.current_stream(self.dev)
         cs.wait_event(ev)                                 # device-side wait, the host does not block
-        d_lab.record_stream(cs)
+        for t_ in (d_lab if isinstance(d_lab, MixedLabels) else (d_lab,)):
+            t_.record_stream(cs)
         if self.segmenter is not None:
             x, maps, derived = d_img
             x.record_stream(cs)
@@ -435,4 +571,6 @@ class DeviceLoader:
                 self.segmenter.set_label_maps(maps, derived)
             return x, d_lab
         d_img.record_stream(cs)
+        if self.mix is not None:
+            return self.mix(self.tf(d_img), d_lab)
         return self.tf(d_img), d_lab

@@ -16,6 +16,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 import torch
 
 from . import train as T
+from .data import MixedLabels
 
 
 def _sync_time(fn: Callable[[], None], iters: int) -> float:
@@ -111,6 +112,10 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
     """The reference's epoch loop (experiments/mhla_pretrained.py:350-420) with device-side statistics: one host
     sync per EPOCH.  optimizer: train.FusedAdamW (hot path) or any torch.optim optimizer.
     label_smoothing: the TRAINING loss is nn.CrossEntropyLoss(label_smoothing=...)'s; evaluation keeps the plain one.
+    Mixed batches: the train loader may yield (images, data.MixedLabels(labels, lam)) (data.DeviceLoader(mix=...));
+    the training loss is then taken against the mixed targets, and train_acc counts a prediction as right when it is
+    the row's OWN label (labels[b], not the partner's), so under mixing it reads lower than the accuracy on clean
+    images.  Evaluation never mixes.
     schedule: an object with step() (train.WarmupCosine), called after every optimizer step.
     history["grad_norm"] (the epoch mean of the pre-clip global gradient norm, summed on the device) is present
     when the optimizer exposes `grad_norm` (train.FusedAdamW with max_grad_norm or skip_nonfinite).
@@ -148,9 +153,12 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         total = n_batches = 0
         norm_sum = torch.zeros((), device=dev) if track_norm else None
         for images, labels in train_loader:
+            mix_lam = None
+            if isinstance(labels, MixedLabels):
+                labels, mix_lam = labels
             optimizer.zero_grad()
             out = model(images)
-            loss = T.cross_entropy(out, labels, label_smoothing)
+            loss = T.cross_entropy(out, labels, label_smoothing, mix_lam)
             loss.backward()
             optimizer.step()
             if schedule is not None:

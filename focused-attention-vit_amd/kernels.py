@@ -808,9 +808,28 @@ def slic_stage_times(images, n_segments=16, compactness=0.1, sigma=1.0, max_num_
     return out
 
 
-def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0):
+def batch_mix(x, lam, box):
+    """Mixup / CutMix of an fp32 [B, C, H, W] batch with its flip, in place (favit_batch_mix): row b is paired with
+    row B-1-b; box[b] = (y0, y1, x0, x1) non-empty pastes the partner's pixels into the box, an empty box blends
+    lam[b] * x[b] + (1 - lam[b]) * x[B-1-b], and lam[b] == 1 with an empty box leaves the row's bits alone.
+    lam: fp32 [B], box: int32 [B, 4], both on the device (data.BatchMix draws them).  Returns x."""
+    require_gpu(x, lam, box)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("batch_mix: x must be a contiguous fp32 [B, C, H, W] tensor")
+    B, Cn, H, W = x.shape
+    if lam.dtype != torch.float32 or tuple(lam.shape) != (B,) or not lam.is_contiguous():
+        raise TypeError("batch_mix: lam must be a contiguous fp32 [B] tensor")
+    if box.dtype != torch.int32 or tuple(box.shape) != (B, 4) or not box.is_contiguous():
+        raise TypeError("batch_mix: box must be a contiguous int32 [B, 4] tensor of (y0, y1, x0, x1)")
+    _abi.check(_abi.lib().favit_batch_mix(_p(x), _p(lam), _p(box), B, Cn, H, W, _st()), "favit_batch_mix")
+    return x
+
+
+def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0, mix_lam=None):
     """Returns (loss_rows[B], dlogits or None).  label_smoothing = eps in [0, 1): the loss of
-    nn.CrossEntropyLoss(label_smoothing=eps) (favit_cross_entropy_ls); 0 calls favit_cross_entropy."""
+    nn.CrossEntropyLoss(label_smoothing=eps) (favit_cross_entropy_ls); 0 calls favit_cross_entropy.
+    mix_lam (fp32 [B] on the device, read when the kernel runs): the target of row b is lam[b] * onehot(labels[b]) +
+    (1 - lam[b]) * onehot(labels[B-1-b]), the labels of kernels.batch_mix's pairs (favit_cross_entropy_mix)."""
     if not 0.0 <= label_smoothing < 1.0:
         raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
     require_gpu(logits, labels)
@@ -823,7 +842,14 @@ def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0):
     loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
     dlog = torch.empty_like(logits) if grad_scale is not None else None
     gs = 0.0 if grad_scale is None else grad_scale
-    if label_smoothing:
+    if mix_lam is not None:
+        require_gpu(mix_lam)
+        if mix_lam.dtype != torch.float32 or tuple(mix_lam.shape) != (B,) or not mix_lam.is_contiguous():
+            raise TypeError("cross_entropy: mix_lam must be a contiguous fp32 [B] tensor")
+        _abi.check(_abi.lib().favit_cross_entropy_mix(_p(logits), _p(labels), _p(mix_lam), _p(loss_rows), _p(dlog), B,
+                                                      Cn, gs, float(label_smoothing), _st()),
+                   "favit_cross_entropy_mix")
+    elif label_smoothing:
         _abi.check(_abi.lib().favit_cross_entropy_ls(_p(logits), _p(labels), _p(loss_rows), _p(dlog), B, Cn, gs,
                                                      float(label_smoothing), _st()), "favit_cross_entropy_ls")
     else:

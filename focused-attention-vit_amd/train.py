@@ -22,22 +22,25 @@ class _CrossEntropyFn(torch.autograd.Function):
     """nn.CrossEntropyLoss() (mean reduction) forward + gradient in one kernel."""
 
     @staticmethod
-    def forward(ctx, logits, labels, label_smoothing=0.0):
+    def forward(ctx, logits, labels, label_smoothing=0.0, mix_lam=None):
         B = logits.shape[0]
         rows, dlog = K.cross_entropy(logits.contiguous(), labels.contiguous(), grad_scale=1.0 / B,
-                                     label_smoothing=label_smoothing)
+                                     label_smoothing=label_smoothing, mix_lam=mix_lam)
         ctx.save_for_backward(dlog)
         return K.reduce_rows(rows.view(B, 1))[0] / B
 
     @staticmethod
     def backward(ctx, g):
         (dlog,) = ctx.saved_tensors
-        return dlog * g, None, None
+        return dlog * g, None, None, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
-    """nn.CrossEntropyLoss(label_smoothing=label_smoothing)(logits, labels), mean reduction."""
-    return _CrossEntropyFn.apply(logits, labels, float(label_smoothing))
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0,
+                  mix_lam: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.CrossEntropyLoss(label_smoothing=label_smoothing)(logits, labels), mean reduction.
+    mix_lam (fp32 [B] on the device, no gradient): the loss against the Mixup / CutMix target of data.BatchMix,
+    lam[b] * onehot(labels[b]) + (1 - lam[b]) * onehot(labels[B-1-b]), smoothed on top; None: the plain loss."""
+    return _CrossEntropyFn.apply(logits, labels, float(label_smoothing), mix_lam)
 
 
 def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = None,
@@ -589,11 +592,12 @@ def load_checkpoint(path: str, model: torch.nn.Module, opt: Optional[FusedAdamW]
     return ck.get("extra")
 
 
-def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0):
-    """One step of the reference's hot loop; returns the (device) loss tensor, no host sync."""
+def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0, mix_lam=None):
+    """One step of the reference's hot loop; returns the (device) loss tensor, no host sync.
+    mix_lam: the target weights of a batch mixed by data.BatchMix (cross_entropy)."""
     opt.zero_grad()
     logits = model(images)
-    loss = cross_entropy(logits, labels, label_smoothing)
+    loss = cross_entropy(logits, labels, label_smoothing, mix_lam)
     loss.backward()
     opt.step()
     return loss
@@ -617,11 +621,16 @@ class GraphedStep:
       while segment s + 1 replays.  ``segments = 1`` (default without a process group) defers every bucket to step().
 
     Requirements: FusedAdamW (its bf16 weight mirror is refreshed by kernels, not by host-side caching), fixed shapes,
-    and for SPPP models ``model.assume_num_tokens`` set (the per-forward token-count check is a host sync)."""
+    and for SPPP models ``model.assume_num_tokens`` set (the per-forward token-count check is a host sync).
+
+    * Mixed batches (data.BatchMix): the target weights change every step, so they cannot be a by-value argument.  With
+      ``mix=True`` the step owns a static fp32 [B] buffer that the captured loss kernel (favit_cross_entropy_mix) reads
+      when it executes; every call copies its ``mix_lam`` into it, and a call without one fills it with ones, which
+      gives the loss and the gradient of the unmixed step bit for bit."""
 
     def __init__(self, model: torch.nn.Module, opt: FusedAdamW, images: torch.Tensor, labels: torch.Tensor,
                  warmup: int = 3, segments: Optional[int] = None, static_inputs: bool = False,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, mix: bool = False):
         """static_inputs: `images` / `labels` themselves are the buffers the captured kernels read (no clone at capture,
         no copy per call when the step is called with these same tensors): for a producer that writes every batch into
         fixed device buffers (bench.py's resident synthetic batch).  Default: private copies, one device-to-device copy
@@ -631,6 +640,7 @@ class GraphedStep:
         self.model, self.opt = model, opt
         self.label_smoothing = float(label_smoothing)          # (a by-value kernel argument: frozen into the graph)
         self.x, self.y = (images, labels) if static_inputs else (images.clone(), labels.clone())
+        self.lam = torch.ones(labels.shape[0], dtype=torch.float32, device=labels.device) if mix else None
         syncs = [g["sync"] for g in opt.groups if g["sync"] is not None and g["sync"]._active]
         self._syncs = syncs
         if segments is None:
@@ -697,7 +707,7 @@ class GraphedStep:
                 self.epoch.add_(1)
             self.opt.zero_grad()
             with F.encoder_segments(self.segments) as seg:
-                loss = cross_entropy(self.model(self.x), self.y, self.label_smoothing)
+                loss = cross_entropy(self.model(self.x), self.y, self.label_smoothing, self.lam)
             bounds = list(seg.boundaries)
         if graphs is not None:
             self.loss = loss
@@ -711,11 +721,19 @@ class GraphedStep:
                 out, leaf = bounds[k - 1]
                 heads, grads = [out], [leaf.grad]
 
-    def __call__(self, images: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def __call__(self, images: torch.Tensor, labels: torch.Tensor,
+                 mix_lam: Optional[torch.Tensor] = None) -> torch.Tensor:
         if images is not self.x:
             self.x.copy_(images, non_blocking=True)
         if labels is not self.y:
             self.y.copy_(labels, non_blocking=True)
+        if self.lam is not None:
+            if mix_lam is None:
+                self.lam.fill_(1.0)
+            else:
+                self.lam.copy_(mix_lam, non_blocking=True)
+        elif mix_lam is not None:
+            raise ValueError("GraphedStep: mix_lam needs a step captured with mix=True")
         self.opt.refresh_mirrors()         # (host-side version check; a cast only after an outside edit of the weights)
         for st in self._map_states:        # (likewise: label maps edited in place without update_label_maps)
             st.refresh_if_stale()

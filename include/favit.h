@@ -525,6 +525,33 @@ int favit_adamw_clip_ema(float* p, const float* g, float* m, float* v, void* p_b
  * address changes, so a captured graph that reads a / a_bf16 stays valid; two calls restore every bit. */
 int favit_swap_params(float* a, float* b, void* a_bf16, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batch mixing (additive in ABI 8): Mixup / CutMix of a batch with its own flip (timm's Mixup), and the loss of the
+ * mixed targets.  Row b is paired with row p = B-1-b; with B odd the middle row is its own partner and never changes.
+ * ---------------------------------------------------------------------------------- */
+/* In place on x, fp32 [B, C, H, W]; lam [B] fp32 and box [B, 4] int32 = (y0, y1, x0, x1), half-open, are DEVICE arrays
+ * read when the kernel executes.  With a, q the values of rows b and p before the call, per row b:
+ *   box non-empty (y0 < y1 and x0 < x1): pixels with y0 <= y < y1 and x0 <= x < x1, in every channel, become q; the
+ *                                        others keep their bits (CutMix; lam[b] is not read by the image side)
+ *   box empty, lam[b] != 1:              x = fmaf(lam, a, (1 - lam) * q)                              (Mixup)
+ *   box empty, lam[b] == 1:              the row keeps its bits
+ * One work item owns the same 16 bytes (4 bytes when W % 4 != 0 or x is not 16-byte aligned) of both rows of a pair,
+ * reads both old values and writes both new ones, so in place is safe: a full Mixup reads and writes the batch once, a
+ * CutMix row moves only the 16-byte groups its box meets, a pair of unchanged rows moves nothing.  The box only
+ * selects between the two in-range addresses, so no lam / box content can cause an out-of-range access.  C * H * W
+ * must be below 2^31 (else FAVIT_ERR_UNSUPPORTED).  B == 1 succeeds and does nothing. */
+int favit_batch_mix(float* x, const float* lam, const int32_t* box, int32_t B, int32_t C, int32_t H, int32_t W,
+                    void* stream);
+/* favit_cross_entropy_ls against the target  t[b] = lam[b] * onehot(labels[b]) + (1 - lam[b]) * onehot(labels[B-1-b]):
+ *   loss_rows[b] = lse - (1 - eps) * (lam * x[y_b] + (1 - lam) * x[y_p]) - eps * mean_c(x)
+ *   dlogits      = (softmax - (1 - eps) * (lam * [c == y_b] + (1 - lam) * [c == y_p]) - eps / C) * grad_scale
+ * lam: DEVICE array [B], read when the kernel executes (a captured graph sees the values of each replay).  lam[b] == 1
+ * gives the bits of favit_cross_entropy_ls with the same eps (eps = 0: of favit_cross_entropy) for finite logits.  An
+ * own or a partner label out of range gives a NaN loss row, never an out-of-range read.  Health word as there. */
+int favit_cross_entropy_mix(const float* logits, const int64_t* labels, const float* lam, float* loss_rows,
+                            float* dlogits, int32_t B, int32_t C, float grad_scale, float label_smoothing,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,15 @@ def parse_args(argv=None):
     ap.add_argument("--skip_nonfinite", action="store_true",
                     help="do not apply an update whose gradient norm is inf / NaN (counted, reported at the end)")
     ap.add_argument("--label_smoothing", type=float, default=0.0, help="training loss only; evaluation keeps plain cross-entropy")
+    ap.add_argument("--mixup_alpha", type=float, default=0.0,
+                    help="Mixup of every training batch with its flip, lam ~ Beta(a, a) (default 0: off; timm uses 0.8)")
+    ap.add_argument("--cutmix_alpha", type=float, default=0.0,
+                    help="CutMix of every training batch with its flip (default 0: off; timm uses 1.0)")
+    ap.add_argument("--mix_prob", type=float, default=1.0, help="--mixup_alpha / --cutmix_alpha: probability of mixing a draw")
+    ap.add_argument("--mix_switch_prob", type=float, default=0.5,
+                    help="with both alphas > 0: probability that a draw is CutMix rather than Mixup")
+    ap.add_argument("--mix_mode", default="batch", choices=["batch", "elem"],
+                    help="one draw per batch, or one per image")
     ap.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine"],
                     help="cosine: linear warm-up over --warmup_epochs, then half a cosine to zero over the remaining epochs")
     ap.add_argument("--warmup_epochs", type=float, default=0.0, help="--lr_schedule cosine: length of the linear warm-up")
@@ -243,7 +252,10 @@ def main(argv=None):
     seg = getattr(model, "segmentation", None)
     if train_src is None:
         train_src, test_src = Epochs(xtr, ytr, True), Epochs(xte, yte, False)
-    train_loader = pkg.data.DeviceLoader(train_src, tfs["train"], segmenter=seg)
+    mix = None
+    if a.mixup_alpha > 0 or a.cutmix_alpha > 0:           # training batches only; seeded like the transforms
+        mix = pkg.data.BatchMix(a.mixup_alpha, a.cutmix_alpha, a.mix_prob, a.mix_switch_prob, a.mix_mode, seed=a.seed)
+    train_loader = pkg.data.DeviceLoader(train_src, tfs["train"], segmenter=seg, mix=mix)
     test_loader = pkg.data.DeviceLoader(test_src, tfs["test"], segmenter=seg)
     work = train_loader.compute_stream if seg is not None else torch.cuda.current_stream()
     work.wait_stream(torch.cuda.current_stream())
