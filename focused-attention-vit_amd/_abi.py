@@ -51,6 +51,19 @@ class SdpaDesc(C.Structure):
     ]
 
 
+class BlockDesc(C.Structure):
+    """Mirror of favit_mhla_block_t (include/favit.h)."""
+    _fields_ = [
+        ("x", vp), ("tape", vp), ("g1", vp), ("b1", vp), ("g2", vp), ("b2", vp), ("weff", vp), ("beff", vp),
+        ("wproj", vp), ("bproj", vp), ("wfc1", vp), ("bfc1", vp), ("wfc2", vp), ("bfc2", vp),
+        ("tape_bytes", i64),
+        ("B", i32), ("n", i32), ("D", i32), ("H", i32), ("W", i32), ("hidden", i32), ("training", i32), ("eps", f32),
+    ]
+
+
+BLOCK_TAPE_SLOTS = ("xn1", "mu1", "rs1", "qkv", "o", "lse", "x1", "xn2", "mu2", "rs2", "h", "pre", "x2")
+BLOCK_BWD_SLOTS = ("dpre", "dxn2", "g1_f32", "g1_lp", "do", "dqkv", "dxn1", "g_out_f32", "g_out_lp", "part1", "part2")
+
 _SIGS = {
     "favit_abi_version": ([], C.c_int),
     "favit_strerror": ([C.c_int], C.c_char_p),
@@ -95,6 +108,10 @@ _SIGS = {
     "favit_embed_prologue_bwd": ([vp, vp, C.c_int, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_rows_cut_fwd": ([vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
     "favit_rows_cut_bwd": ([vp, vp, vp, C.c_int, i32, i32, i32, i32, i32, vp], C.c_int),
+    "favit_mhla_block_tape_layout": ([C.POINTER(BlockDesc), C.POINTER(i64)], C.c_int64),
+    "favit_mhla_block_bwd_layout": ([C.POINTER(BlockDesc), i32, C.POINTER(i64)], C.c_int64),
+    "favit_mhla_block_fwd": ([C.POINTER(BlockDesc), vp], C.c_int),
+    "favit_mhla_block_bwd": ([C.POINTER(BlockDesc), vp, vp, vp, i64, i32, vp], C.c_int),
     "favit_dropout": ([vp, vp, C.c_int, i64, f32, u64, vp], C.c_int),
     "favit_sppp_map_patches": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_sppp_pool_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),

@@ -741,31 +741,44 @@ class MHLAChain:
         H, hd = self.H, D // self.H
         dym = K.dropout(dy_lp, pp, sp) if (pp > 0 and not premasked) else dy_lp
         do = lin_bwd_x(dym, wp_c, M, D, D, xn.dtype, site=wp)
-        dwp, dbp = lin_bwd_w(dym, o, M, D, D, wp=wp, bp=bp)
+        dwp, dbp = self.proj_grads(dym, o, prm)
         dqkv = K.mhla_attn_bwd(qkv, do, B, L, H, hd, self.W, mask, pa, sa, o=o if lse is not None else None, lse=lse)
         dxn = lin_bwd_x(dqkv, weff, M, 3 * D, D, xn.dtype, site=wqkv)
+        return dxn, self.qkv_grads(dqkv, xn, prm) + [dwp, dbp]
+
+    @staticmethod
+    def proj_grads(dym, o, prm):
+        M, D = o.shape
+        return lin_bwd_w(dym, o, M, D, D, wp=prm[4], bp=prm[5])
+
+    def qkv_grads(self, dqkv, xn, prm):
+        """[dwqkv, dbqkv, dwl, dbl] (None where a gradient buffer took the result) from the gradient of the folded
+        projection's output: the dWeff GEMM and the latent_proj fold backward, launched or queued.  Shared by bwd and
+        the native block backward (EncoderOp), which differ only in who launched the input-gradient chain."""
+        wqkv, bqkv, wl, bl = prm[:4]
+        M, D = xn.shape
+        H = self.H
         dweff, dbeff = lin_bwd_w(dqkv, xn, M, 3 * D, D)
         # (dW2, dW1, dWproj, dWeff join the grouped weight-gradient launch, which may wait for further blocks; the
         # batched fold below consumes dWeff only after that launch -- EncoderOp.bwd flushes in that order)
         tg = [_gt(p) for p in (wqkv, bqkv, wl, bl)]
         if all(t is not None for t in tg) and _DEFER["on"]:
             _DEFER["fold"].append((dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), tg, H, (wqkv, bqkv, wl, bl)))
-            return dxn, [None, None, None, None, dwp, dbp]
+            return [None, None, None, None]
         if (_DEFER["on"] and not wqkv.requires_grad and not bqkv.requires_grad and tg[2] is not None and tg[3] is not None):
             # frozen qkv projection, trainable latent_proj (experiments/sppp_mhla_pretrained.py:236-247): the batched
             # launch with its qkv half switched off, straight into the latent_proj gradient buffers
             _DEFER["fold"].append((dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), [None, None, tg[2], tg[3]], H,
                                    (wl, bl)))
-            return dxn, [None, None, None, None, dwp, dbp]
+            return [None, None, None, None]
         flush_wgrads()                      # the fold runs now: dWeff must have been launched
         if all(t is not None for t in tg):
             with _side_stream(dweff, dbeff):
                 K.mhla_fold_bwd(dweff, dbeff, wqkv, bqkv, wl, H, out=tg)
                 _ready(wqkv, bqkv, wl, bl)
-            return dxn, [None, None, None, None, dwp, dbp]
+            return [None, None, None, None]
         join_side_stream()
-        dwqkv, dbqkv, dwl, dbl = K.mhla_fold_bwd(dweff, dbeff, wqkv, bqkv, wl, H)
-        return dxn, [dwqkv, dbqkv, dwl, dbl, dwp, dbp]
+        return list(K.mhla_fold_bwd(dweff, dbeff, wqkv, bqkv, wl, H))
 
 
 class DenseChain:
@@ -904,11 +917,17 @@ class MLPChain:
                                             want_pre=True, drop=(p, s1))
             ln[3][:] = [xn, mu, rs]
         else:
-            sg = xn.dtype != torch.float32
+            sg = self.saves_gelu_grad(xn.dtype)
             h, pre = lin_fwd(xn, w1_c, b1.detach(), M, Hd, D, xn.dtype, act=ACT_GELU_SAVEGRAD if sg else ACT_GELU,
                              want_pre=True, drop=(p, s1), site=w1)
         y = lin_fwd(h, w2_c, b2.detach(), M, Do, Hd, torch.float32, residual=residual, drop=(p, s2), site=w2)
         return y, (xn, (pre, sg), h, w1_c, w2_c, p, s1, s2, prm)
+
+    @staticmethod
+    def saves_gelu_grad(cdt) -> bool:
+        """Does fc1 run ACT_GELU_SAVEGRAD in this compute dtype (then backward multiplies by the saved GELU', ACT_MULAUX)?
+        The native block chain (csrc/block.hip) is the bf16 case of this rule."""
+        return cdt != torch.float32
 
     @staticmethod
     def out_dropout(saved):
@@ -921,10 +940,19 @@ class MLPChain:
         Hd, Do = w1_c.shape[0], w2_c.shape[0]
         dym = K.dropout(dy_lp, p, s2) if (p > 0 and not premasked) else dy_lp
         dpre = lin_bwd_x(dym, w2_c, M, Do, Hd, xn.dtype, dgelu_pre=pre, pre_is_grad=sg, drop=(p, s1), site=w2)
-        dw2, db2 = lin_bwd_w(dym, h, M, Do, Hd, wp=w2, bp=b2)
+        dw2, db2 = self.fc2_grads(dym, h, prm)
         dxn = lin_bwd_x(dpre, w1_c, M, Hd, D, xn.dtype, site=w1)
-        dw1, db1 = lin_bwd_w(dpre, xn, M, Hd, D, wp=w1, bp=b1)
+        dw1, db1 = self.fc1_grads(dpre, xn, prm)
         return dxn, [dw1, db1, dw2, db2]
+
+    # the two weight-gradient problems, as bwd and the native block backward (EncoderOp) both queue them
+    @staticmethod
+    def fc2_grads(dym, h, prm):
+        return lin_bwd_w(dym, h, dym.shape[0], dym.shape[1], h.shape[1], wp=prm[2], bp=prm[3])
+
+    @staticmethod
+    def fc1_grads(dpre, xn, prm):
+        return lin_bwd_w(dpre, xn, dpre.shape[0], dpre.shape[1], xn.shape[1], wp=prm[0], bp=prm[1])
 
 
 # ------------------------------------------------------------------------------------
@@ -1100,6 +1128,75 @@ def cls_only_cuts(specs: Sequence["BlockSpec"], L: int, mask, training: bool):
     return plan if any(c is not None for c in plan) else None
 
 
+# Native block chains: where a block is MHLA + MLP in bf16 without mask or dropout, the seven
+# launches of its forward and the seven of its input-gradient chain are issued by ONE library call each
+# (favit_mhla_block_fwd / _bwd) instead of one Python wrapper call each, with its allocations and its descriptor.  The
+# launches and their arguments are the same, so results are bit-identical; the switches below select the path.
+_NATIVE = {"on": True}
+
+
+def set_native_blocks(on: bool) -> None:
+    """A/B switch of the native block chains (default on).  FAVIT_NO_NATIVE_BLOCKS=1 in the environment (read at each
+    call, so it shows among a benchmark's knobs) switches them off as well."""
+    _NATIVE["on"] = bool(on)
+
+
+def _native_blocks_on() -> bool:
+    """The conditions that do not depend on the block.  K.GEMM_TRACE has to see every GEMM; the side stream and the
+    fused LayerNorm are launch patterns of the Python chains only."""
+    return (_NATIVE["on"] and K.GEMM_TRACE is None and not _SIDE["enabled"] and not _LN_FUSE
+            and get_compute_mode() == "bf16" and not os.environ.get("FAVIT_NO_NATIVE_BLOCKS"))
+
+
+def _carve(flat, off, shape):
+    """A contiguous view of `shape` at element offset `off` of the flat tensor (one op; it shares the storage, so it
+    keeps the whole allocation alive for as long as it lives)."""
+    st, n = [], 1
+    for d in reversed(shape):
+        st.append(n)
+        n *= d
+    return torch.as_strided(flat, shape, tuple(reversed(st)), off)
+
+
+class _NativeTape:
+    """What a native block forward left for backward: ONE device allocation (buf, carved by plan.off) plus the
+    references the Python tape tuple holds.  Tensor views of the allocation are made only when somebody asks:
+    the native backward needs four of them (the weight-gradient operands), the Python backward all (unpack)."""
+    __slots__ = ("plan", "buf", "x", "ln", "pa", "pm", "weff", "wc", "cut", "_bf", "_f32")
+
+    def __init__(self, plan, buf, x, ln, pa, pm, weff, wc, cut):
+        self.plan, self.buf, self.x, self.ln, self.pa, self.pm, self.weff, self.wc, self.cut = \
+            plan, buf, x, ln, pa, pm, weff, wc, cut
+        self._bf = self._f32 = None
+
+    def bf(self, name, *shape):
+        if self._bf is None:
+            self._bf = self.buf.view(torch.bfloat16)
+        return _carve(self._bf, self.plan.off[name][0] // 2, shape)
+
+    def f32(self, name, *shape):
+        if self._f32 is None:
+            self._f32 = self.buf.view(torch.float32)
+        return _carve(self._f32, self.plan.off[name][0] // 4, shape)
+
+    def unpack(self):
+        """The tape tuple EncoderOp.fwd's Python path would have built for this block (EncoderOp.bwd reads it)."""
+        pl = self.plan
+        M, D, Hd = pl.M, pl.D, pl.hidden
+        (g1, b1, g2, b2), (wp_c, w1_c, w2_c) = self.ln, self.wc
+        lse = self.f32("lse", pl.B, pl.H, pl.n) if pl.off["lse"][1] else None
+        sa = (self.bf("xn1", M, D), self.weff, self.bf("qkv", M, 3 * D), self.bf("o", M, D), wp_c, None, pl.B, pl.n,
+              0.0, 0, 0.0, 0, self.pa, lse)
+        sm = (self.bf("xn2", M, D), (self.bf("pre", M, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)), self.bf("h", M, Hd),
+              w1_c, w2_c, 0.0, 0, 0, self.pm)
+        return (self.x, self.f32("mu1", M), self.f32("rs1", M), (g1, b1), sa, self.f32("x1", M, D), self.f32("mu2", M),
+                self.f32("rs2", M), (g2, b2), sm, (self.pa, self.pm), self.cut)
+
+
+def _tape_cut(tp):
+    return tp.cut if isinstance(tp, _NativeTape) else tp[11]
+
+
 class EncoderOp:
     """A stack of pre-LN blocks on the fp32 residual stream [B, L, D]:
     x += attn(LN1(x)); x += mlp(LN2(x)).
@@ -1138,6 +1235,7 @@ class EncoderOp:
         if 2 <= len(idx) <= 32 and len({(self.blocks[i].attn.H, tuple(q[0].shape)) for i, q in zip(idx, fp)}) == 1:
             for bi, we in zip(idx, K.mhla_fold_fwd_multi(fp, self.blocks[idx[0]].attn.H, cdt)):
                 pre[bi] = we
+        native = self.mask is None and x.is_cuda and _native_blocks_on()
         off = 0
         for bi, bs in enumerate(self.blocks):
             p = list(prm[off:off + bs.n])
@@ -1154,6 +1252,12 @@ class EncoderOp:
                 cut = (L, ca, cb)
                 L = ca + cb
                 M = B * L
+            if native and pre[bi] is not None:
+                nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut)
+                if nt is not None:
+                    tapes.append(nt)
+                    x = nt.f32("x2", M, D)
+                    continue
             fuse = fuse_ok and M <= 16384
             if fuse and isinstance(bs.attn, (MHLAChain, DenseChain)):
                 o1 = [None, None, None]
@@ -1177,12 +1281,82 @@ class EncoderOp:
             x = x2
         return x.reshape(B, L, D), (tapes, B, L_in, D)
 
+    def _fwd_native(self, bs, p, x, B, L, D, pre, cut):
+        """One block's forward as one library call, or None where this block runs the Python chains: not MHLA + MLP, a
+        dropout that is active in this mode, parameters of another dtype or shape than the chain assumes, a geometry
+        the library declines (favit_mhla_block_tape_layout), or a declined call (nothing was launched then)."""
+        at, ml = bs.attn, bs.mlp
+        if not (isinstance(at, MHLAChain) and isinstance(ml, MLPChain)) or len(p) != 14:
+            return None
+        if self.training and (at.p_attn > 0 or at.p_proj > 0 or ml.p > 0):
+            return None
+        g1, b1, wqkv, bqkv, wl, bl, wp, bp, g2, b2, w1, c1, w2, c2 = p
+        Hd = w1.shape[0]
+        if tuple(w2.shape) != (D, Hd) or tuple(w1.shape) != (Hd, D) or tuple(wp.shape) != (D, D):
+            return None
+        if any(t.dtype != torch.float32 or not t.is_contiguous() for t in (g1, b1, g2, b2, bp, c1, c2)):
+            return None
+        weff, beff = pre
+        wc = (wcast(wp), wcast(w1), wcast(w2))
+        if weff.dtype != torch.bfloat16 or any(w.dtype != torch.bfloat16 or not w.is_contiguous() for w in wc):
+            return None
+        # the plan (descriptor geometry + layouts) is kept on the block's first parameter, per shape: it lives and
+        # dies with the block
+        plans = getattr(g1, "_favit_blocks", None)
+        if plans is None:
+            plans = g1._favit_blocks = {}
+        key = (B, L, D, at.H, at.W, Hd, bool(self.training))
+        if key not in plans:
+            plans[key] = K.mhla_block_plan(*key)
+        plan = plans[key]
+        if plan is None:
+            return None
+        buf = torch.empty(plan.tape_bytes, dtype=torch.uint8, device=x.device)
+        if K.mhla_block_fwd(plan, x, buf, g1, b1, g2, b2, weff, beff, wc[0], bp, wc[1], c1, wc[2], c2) != 0:
+            return None
+        return _NativeTape(plan, buf, x, (g1, b1, g2, b2), p[2:8], p[10:], weff, wc, cut)
+
+    def _bwd_native(self, bs, tp, g, g_lp):
+        """The input-gradient chain of a block with a native tape as one library call, then what MLPChain.bwd,
+        MHLAChain.bwd and ln_bwd do besides launching it: the weight-gradient problems and the deferred folds, in
+        their order.  Returns (g, g_lp or None, attention grads, mlp grads), or None where the Python chains have to run
+        (a LayerNorm parameter without a gradient buffer, a gradient of another layout, a declined call).
+        Lifetime: every buffer the queued launches read or write is a VIEW of the arena or of the tape, held by
+        _WG["list"] / _DEFER until those launches have been issued; nothing is freed or reused before."""
+        plan = tp.plan
+        g1, b1, g2, b2 = tp.ln
+        tg = [_gt(q) for q in tp.ln]
+        if any(t is None for t in tg):
+            return None
+        M, D, Hd = plan.M, plan.D, plan.hidden
+        if (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (M, D) or not g.is_contiguous()
+                or tuple(g_lp.shape) != (M, D) or not g_lp.is_contiguous()):
+            return None
+        want_lp = tp.cut is None
+        arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
+        wp_c, w1_c, w2_c = tp.wc
+        if K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp) != 0:
+            return None
+        bo = plan.boff[want_lp]
+        abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
+        part = lambda k: _carve(af, bo[k][0] // 4, (2, plan.nparts, D))
+        g1_lp = _carve(abf, bo["g1_lp"][0] // 2, (M, D))
+        dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
+        dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", M, Hd), tp.pm)
+        dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (M, Hd)), tp.bf("xn2", M, D), tp.pm)
+        _DEFER["ln"].append((part("part2"), tg[2], tg[3], (g2, b2)))
+        dwp, dbp = bs.attn.proj_grads(g1_lp, tp.bf("o", M, D), tp.pa)
+        ga = bs.attn.qkv_grads(dqkv, tp.bf("xn1", M, D), tp.pa) + [dwp, dbp]
+        _DEFER["ln"].append((part("part1"), tg[0], tg[1], (g1, b1)))
+        g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
+        return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, [dw1, db1, dw2, db2]
+
     def bwd(self, saved, dy, needs):
         tapes, B, L, D = saved
         g = dy.reshape(-1, D)
         g_lp = _as_cdt(g)
         grads = []
-        begin_wgrads(per_block=any(tp[11] is not None for tp in tapes))
+        begin_wgrads(per_block=any(_tape_cut(tp) is not None for tp in tapes))
         begin_deferred()
         begin_zero_pool(sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)), dy.device)
 
@@ -1210,29 +1384,42 @@ class EncoderOp:
             order = list(zip(reversed(self.blocks), reversed(tapes)))
             premasked = False
             for bi, (bs, tp) in enumerate(order):
-                x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa_, _), cut = tp
-                dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
-                pd = bs.attn.out_dropout(sa) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
-                # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
-                # written, since a branch with output dropout gets it pre-masked)
-                g, g_lp, dg2, db2 = ln_bwd(dxn2, x1, g2, b2, mu2, rs2, g, pd,
-                                           q8=_q8_request(bs.attn, pa_, "bwd", D) if hasattr(bs.attn, "out_dropout") else None)
-                dxn1, ga = (bs.attn.bwd(sa, g_lp, premasked=pd[0] > 0) if hasattr(bs.attn, "out_dropout")
-                            else bs.attn.bwd(sa, g_lp))
-                pd = (0.0, 0)
-                q8n = None
-                if bi + 1 < len(order):
+                # what the low-precision copy of this block's input gradient has to carry for the block below
+                # (a native tape there: no dropout was active and the mode is bf16, so nothing)
+                pd_n, q8n = (0.0, 0), None
+                if bi + 1 < len(order) and not isinstance(order[bi + 1][1], _NativeTape):
                     nbs, ntp = order[bi + 1]
-                    pd = nbs.mlp.out_dropout(ntp[9])
+                    pd_n = nbs.mlp.out_dropout(ntp[9])
                     q8n = _q8_request(nbs.mlp, ntp[10][1], "bwd", D)       # the next block's fc2 input-gradient GEMM
-                premasked = pd[0] > 0
-                g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd, q8=q8n, want_lp=cut is None)
+                done = None
+                if isinstance(tp, _NativeTape):
+                    if not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"] and _native_blocks_on():
+                        done = self._bwd_native(bs, tp, g, g_lp)
+                    if done is None:
+                        tp = tp.unpack()
+                if done is not None:
+                    g, g_lp, ga, gm = done
+                    dg1 = db1 = dg2 = db2 = None
+                    cut, lp_dt = tp.cut, torch.bfloat16
+                else:
+                    x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa_, _), cut = tp
+                    dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
+                    pd = bs.attn.out_dropout(sa) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
+                    # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
+                    # written, since a branch with output dropout gets it pre-masked)
+                    g, g_lp, dg2, db2 = ln_bwd(dxn2, x1, g2, b2, mu2, rs2, g, pd,
+                                               q8=_q8_request(bs.attn, pa_, "bwd", D) if hasattr(bs.attn, "out_dropout") else None)
+                    dxn1, ga = (bs.attn.bwd(sa, g_lp, premasked=pd[0] > 0) if hasattr(bs.attn, "out_dropout")
+                                else bs.attn.bwd(sa, g_lp))
+                    g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd_n, q8=q8n, want_lp=cut is None)
+                    lp_dt = dxn1.dtype
+                premasked = pd_n[0] > 0
                 if cut is not None:
                     # this block ran on its (head, tail) rows: back to the rows of the block below, zeros in between,
                     # with the compute-dtype copy that block's backward GEMMs read written in the same pass
                     n_in, ca, cb = cut
-                    more = bi + 1 < len(order) and g.dtype != dxn1.dtype
-                    g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=dxn1.dtype if more else None)
+                    more = bi + 1 < len(order) and g.dtype != lp_dt
+                    g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dt if more else None)
                     g = g.reshape(B * n_in, D)
                     g_lp = g_lp.reshape(B * n_in, D) if g_lp is not None else g
                 if flush_wgrads(force=False) and _STATE["grad_ready"] is not None:

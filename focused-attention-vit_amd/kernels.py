@@ -548,6 +548,72 @@ def mhla_attn_bwd(qkv, dout, B, L, H, hd, W, mask=None, p=0.0, seed=0, o=None, l
     return dqkv
 
 
+class BlockPlan:
+    """What favit_mhla_block_fwd / _bwd need for one block at one shape, kept from step to step: the descriptor with
+    its geometry filled in and the two layouts (include/favit.h).  off / boff map slot names to (byte offset, bytes);
+    boff and bwd_bytes are indexed by want_lp_out (0: a row cut follows the block's backward)."""
+    __slots__ = ("desc", "ref", "M", "D", "hidden", "B", "n", "H", "nparts", "tape_bytes", "off", "bwd_bytes", "boff")
+
+
+def mhla_block_plan(B, n, D, H, W, hidden, training, eps=1e-5) -> Optional[BlockPlan]:
+    """The layout queries for one block geometry (host arithmetic, once per shape), or None where the native chain
+    does not take it (D / H != 64, hidden not a multiple of 8, a row count the lse attention kernels decline)."""
+    d = _abi.BlockDesc()
+    d.B, d.n, d.D, d.H, d.W, d.hidden, d.training, d.eps = B, n, D, H, W, hidden, int(bool(training)), eps
+    lib = _abi.lib()
+    to = (C.c_int64 * len(_abi.BLOCK_TAPE_SLOTS))()
+    tape_bytes = lib.favit_mhla_block_tape_layout(C.byref(d), to)
+    if tape_bytes < 0:
+        return None
+    p = BlockPlan()
+    p.desc, p.ref, p.M, p.D, p.hidden, p.B, p.n, p.H = d, C.byref(d), B * n, D, hidden, B, n, H
+    p.nparts = int(min(2048, (B * n + 3) // 4))
+    p.tape_bytes = d.tape_bytes = tape_bytes
+    ends = list(to[1:]) + [tape_bytes]
+    p.off = {k: (to[i], ends[i] - to[i]) for i, k in enumerate(_abi.BLOCK_TAPE_SLOTS)}
+    p.bwd_bytes, p.boff = [], []
+    for want_lp in (0, 1):
+        bo = (C.c_int64 * len(_abi.BLOCK_BWD_SLOTS))()
+        nb = lib.favit_mhla_block_bwd_layout(C.byref(d), want_lp, bo)
+        ends = list(bo[1:]) + [nb]
+        p.bwd_bytes.append(nb)
+        p.boff.append({k: (bo[i], ends[i] - bo[i]) for i, k in enumerate(_abi.BLOCK_BWD_SLOTS)})
+    return p
+
+
+def _block_code(code: int, what: str) -> int:
+    """0, or the negative code of a DECLINED call (nothing was launched: the caller issues the launches itself); a
+    failed launch raises."""
+    if code == _abi.ERR_LAUNCH:
+        _abi.check(code, what)
+    return code
+
+
+def mhla_block_fwd(plan: BlockPlan, x, tape, g1, b1, g2, b2, weff, beff, wproj, bproj, wfc1, bfc1, wfc2, bfc2) -> int:
+    """The forward chain of one block (favit_mhla_block_fwd) on the current stream.  tape: uint8 device tensor of
+    plan.tape_bytes.  All pointers of the descriptor are rewritten (they may change from step to step); the geometry
+    and the layout stay.  Returns 0 or the code of a declined call."""
+    d = plan.desc
+    d.x, d.tape, d.tape_bytes = x.data_ptr(), tape.data_ptr(), tape.numel()
+    d.g1, d.b1, d.g2, d.b2 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr()
+    d.weff, d.beff, d.wproj, d.bproj = weff.data_ptr(), beff.data_ptr(), wproj.data_ptr(), bproj.data_ptr()
+    d.wfc1, d.bfc1, d.wfc2, d.bfc2 = wfc1.data_ptr(), bfc1.data_ptr(), wfc2.data_ptr(), bfc2.data_ptr()
+    return _block_code(_abi.lib().favit_mhla_block_fwd(plan.ref, _st()), "favit_mhla_block_fwd")
+
+
+def mhla_block_bwd(plan: BlockPlan, x, tape, g1, g2, weff, wproj, wfc1, wfc2, g, g_lp, arena, want_lp_out: bool) -> int:
+    """The input-gradient chain of one block (favit_mhla_block_bwd).  g / g_lp: gradient of the block's output, fp32 and
+    bf16 [M, D]; arena: uint8 device tensor of plan.bwd_bytes[want_lp_out].  Only the pointers the chain reads are
+    rewritten (the biases are not read).  Returns 0 or the code of a declined call."""
+    d = plan.desc
+    d.x, d.tape, d.tape_bytes = x.data_ptr(), tape.data_ptr(), tape.numel()
+    d.g1, d.g2 = g1.data_ptr(), g2.data_ptr()
+    d.weff, d.wproj, d.wfc1, d.wfc2 = weff.data_ptr(), wproj.data_ptr(), wfc1.data_ptr(), wfc2.data_ptr()
+    return _block_code(_abi.lib().favit_mhla_block_bwd(plan.ref, g.data_ptr(), g_lp.data_ptr(), arena.data_ptr(),
+                                                       arena.numel(), int(bool(want_lp_out)), _st()),
+                       "favit_mhla_block_bwd")
+
+
 def _sdpa_desc(q, k, v, o, lse, B, H, Lq, Lk, hd, scale, mask, m_sb, m_sq, p, seed):
     """q, k, v, o: (tensor, element offset, row stride, batch stride, head stride) views (functional._View)."""
     d = SdpaDesc()

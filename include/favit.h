@@ -432,6 +432,61 @@ int favit_rows_cut_fwd(const float* x, float* y, int32_t B, int32_t n_in, int32_
 int favit_rows_cut_bwd(const float* dy, float* dx, void* dx_lp, int lp_dtype, int32_t B, int32_t n_in, int32_t a,
                        int32_t b, int32_t D, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * One MHLA encoder block per call (additive in ABI 8): the kernel chain of a pre-LN block
+ *   x1 = x + proj(attn(qkv(LN1(x))));  x2 = x1 + fc2(gelu(fc1(LN2(x1))))        (models/mhla.py:205-222)
+ * in bf16 compute without mask or dropout, issued by ONE host call per direction.  The calls below launch nothing of
+ * their own: they go through favit_layernorm_fwd / _bwd, favit_gemm and the favit_mhla_attn_*_lse pair with the
+ * arguments a caller issuing the nine launches one by one would pass, so results are bit-identical to that sequence.
+ * Everything the forward leaves for the backward lives in ONE caller-owned device allocation, the tape; the
+ * backward's intermediate and result buffers in a second one.  Both are carved by the layout queries (pure host
+ * arithmetic; every offset a multiple of 256 bytes; slots in the order of the enums' names below):
+ *   tape:  xn1 bf16 [M, D], mu1, rs1 fp32 [M], qkv bf16 [M, 3D], o bf16 [M, D], lse fp32 [B, H, n] (empty unless
+ *          training), x1 fp32 [M, D], xn2 bf16 [M, D], mu2, rs2 fp32 [M], h, pre bf16 [M, hidden], x2 fp32 [M, D]
+ *          (M = B * n; x2 is the block's output)
+ *   bwd:   dpre bf16 [M, hidden], dxn2 bf16 [M, D], g1_f32 fp32 / g1_lp bf16 [M, D] (the stream gradient between the
+ *          two branches), do bf16 [M, D], dqkv bf16 [M, 3D], dxn1 bf16 [M, D], g_out_f32 fp32 / g_out_lp bf16 [M, D]
+ *          (the gradient of x; g_out_lp empty unless want_lp_out), part1, part2 fp32 [2, nparts, D] (dgamma / dbeta
+ *          partial sums of LayerNorm 1 / 2, nparts = min(2048, (M + 3) / 4); NOT folded here: the caller runs
+ *          favit_reduce_rows_multi over them)
+ * The layout queries return the total size in bytes, or a negative FAVIT_ERR_* for a geometry the chains do not take:
+ * D a multiple of 64 with D / H == 64, hidden a multiple of 8, and (n, W) accepted by favit_mhla_attn_lse_supported.
+ * fwd / bwd validate every argument BEFORE the first launch (null pointers, a tape / bwd allocation smaller than its
+ * layout or not 256-byte aligned, the geometry above; bwd also needs training != 0): on such a return nothing has
+ * been launched and the caller issues the launches itself.  A failing launch returns that entry point's code at once.
+ * Not part of the chain: weight gradients (dW = dY^T . X from dpre / dqkv / g_lp / g1_lp and the tape), the
+ * latent_proj fold, the fold of part1 / part2 and the row cuts.
+ * ---------------------------------------------------------------------------------- */
+#define FAVIT_BLOCK_TAPE_SLOTS 13
+#define FAVIT_BLOCK_BWD_SLOTS 11
+typedef struct favit_mhla_block {
+  const float* x;       /* block input: fp32 [B*n, D], the residual stream */
+  void* tape;           /* tape_bytes >= the tape layout's size */
+  const float* g1;      /* norm1 weight, bias; norm2 weight, bias: fp32 [D] */
+  const float* b1;
+  const float* g2;
+  const float* b2;
+  const void* weff;     /* folded qkv weight bf16 [3D, D] and bias fp32 [3D] (favit_mhla_fold_fwd) */
+  const float* beff;
+  const void* wproj;    /* bf16 [D, D], fp32 [D] */
+  const float* bproj;
+  const void* wfc1;     /* bf16 [hidden, D], fp32 [hidden] */
+  const float* bfc1;
+  const void* wfc2;     /* bf16 [D, hidden], fp32 [D] */
+  const float* bfc2;
+  int64_t tape_bytes;
+  int32_t B, n, D, H, W, hidden;
+  int32_t training;     /* != 0: the forward saves lse and the backward may follow */
+  float eps;
+} favit_mhla_block_t;
+int64_t favit_mhla_block_tape_layout(const favit_mhla_block_t* desc, int64_t* offsets_out /* [13] or NULL */);
+int64_t favit_mhla_block_bwd_layout(const favit_mhla_block_t* desc, int32_t want_lp_out,
+                                    int64_t* offsets_out /* [11] or NULL */);
+int favit_mhla_block_fwd(const favit_mhla_block_t* desc, void* stream);
+/* g_f32 / g_lp: the gradient of x2, fp32 and bf16 [M, D]. */
+int favit_mhla_block_bwd(const favit_mhla_block_t* desc, const float* g_f32, const void* g_lp, void* bwd_buffers,
+                         int64_t bwd_bytes, int32_t want_lp_out, void* stream);
+
 /* Inverted dropout with a counter-based RNG (nn.Dropout sites, models/vit.py:136,138,
  * 102, mhla.py:159); the mask is recomputed from (seed, index) in backward. */
 int favit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t seed, void* stream);

@@ -32,7 +32,8 @@ import torch
 PATTERN = 0x7FC07FC0
 _NO_LAUNCH = {"favit_abi_version", "favit_strerror", "favit_set_dropout_epoch", "favit_gemm_last_kernel",
               "favit_gemm_grouped_tn_workspace", "favit_mhla_attn_lse_supported", "favit_slic_features_workspace",
-              "favit_slic_cluster_workspace", "favit_grad_norm_workspace"}
+              "favit_slic_cluster_workspace", "favit_grad_norm_workspace", "favit_mhla_block_tape_layout",
+              "favit_mhla_block_bwd_layout"}
 _state = {"installed": False, "calls": 0}
 
 
