@@ -75,7 +75,11 @@ _SIGS = {
     "favit_gemm_grouped_tn": ([C.POINTER(GemmDesc), i32, vp], C.c_int),
     "favit_gemm_grouped_tn_workspace": ([C.POINTER(GemmDesc), i32], C.c_int64),
     "favit_gemm_grouped_tn_ws": ([C.POINTER(GemmDesc), i32, vp, i64, vp], C.c_int),
+    "favit_gemm_grouped_tn_ragged": ([C.POINTER(GemmDesc), i32, vp], C.c_int),
+    "favit_gemm_grouped_tn_ragged_workspace": ([C.POINTER(GemmDesc), i32], C.c_int64),
+    "favit_gemm_grouped_tn_ragged_ws": ([C.POINTER(GemmDesc), i32, vp, i64, vp], C.c_int),
     "favit_gemm_grouped_last_splits": ([], C.c_int),
+    "favit_gemm_grouped_plan": ([C.POINTER(GemmDesc), i32, i32, vp, i32], C.c_int),
     "favit_cast": ([vp, C.c_int, vp, C.c_int, i64, vp], C.c_int),
     "favit_fp8_amax": ([vp, C.c_int, i64, i64, i64, vp, vp], C.c_int),
     "favit_fp8_quantize": ([vp, C.c_int, i64, i64, i64, vp, i64, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -89,6 +93,7 @@ _SIGS = {
     "favit_small_linear_bwd": ([vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
     "favit_reduce_rows": ([vp, i64, vp, i64, i32, i32, vp], C.c_int),
     "favit_reduce_rows_multi": ([i32, vp, vp, vp, i64, i32, vp], C.c_int),
+    "favit_reduce_rows_multi_ragged": ([i32, vp, vp, vp, vp, i32, vp], C.c_int),
     "favit_mhla_fold_fwd": ([vp, vp, vp, vp, vp, C.c_int, vp, vp, i32, i32, vp], C.c_int),
     "favit_mhla_fold_fwd_multi": ([i32, vp, vp, vp, vp, vp, C.c_int, vp, i32, i32, vp], C.c_int),
     "favit_mhla_fold_bwd": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),

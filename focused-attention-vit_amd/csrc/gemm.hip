@@ -2185,9 +2185,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_s64ln_kernel(KParams p, Ln
                                          reinterpret_cast<float*>(smem + wave * WEPI_BYTES), true, p.alpha);
 }
 
-// Grouped weight-gradient launch: up to GROUP_MAX dW = dY^T.X problems that share the token dimension (the four
-// Linear layers of one transformer block -- or, since round 4, of SEVERAL blocks: functional.flush_wgrads collects the
-// problems of up to four blocks, or of the whole encoder at short token counts) run as ONE grid.
+// Grouped weight-gradient launch: up to GROUP_MAX dW = dY^T.X problems (the four Linear layers of one transformer
+// block -- or, since round 4, of SEVERAL blocks: functional.flush_wgrads collects the problems of up to four blocks, or
+// of the whole encoder at short token counts) run as ONE grid.  The problems of one CHUNK share the token dimension;
+// since round 8 different chunks may have different token counts (the blocks of a pruned encoder: 256 x (71, 65, ...,
+// 5) rows at cfg2), each with its own number of K-splits (favit_gemm_grouped_tn_ragged; grouped_plan_ragged).
 //   * chunk = consecutive problems with at most 64 tiles together (one block's four problems at D = 384: 63 tiles =
 //     the 64 workgroup slots of an XCD);  unit = (chunk, K-split);  every unit is pinned to ONE XCD (host-side
 //     longest-first packing into eight queues), so the tiles that stream the same token rows share that XCD's L2;
@@ -2195,9 +2197,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_s64ln_kernel(KParams p, Ln
 //     More blocks per launch need fewer splits to fill the chip -- four cfg2 blocks: 2 splits instead of 8, a quarter
 //     of the slab bytes and of the prologue / epilogue / reduction launches per flop; twelve cfg3 blocks: NO split at
 //     all (no slabs, no reduction kernel, the result is one rounding of one fp32 accumulation chain);
-//   * nsplit > 1: partial tiles go to per-split slabs with plain stores and grouped_reduce_kernel adds the slabs in
-//     split order (deterministic; no fp32 atomics);  nsplit == 1: the tile epilogue writes dW itself (reading the
-//     previous value when the problem accumulates).
+//   * a chunk with more than one split: partial tiles go to that chunk's per-split slabs with plain stores and
+//     grouped_reduce_kernel adds the slabs in split order (deterministic; no fp32 atomics);  a chunk with one split:
+//     the tile epilogue writes dW itself (reading the previous value when the problem accumulates) -- in a ragged
+//     launch the short blocks take this path beside long blocks that are split.
 constexpr int GROUP_MAX = 48;
 constexpr int GROUP_XCD_UNITS = 24;     // units in one XCD's queue, at most
 struct TnProb {          // 64 bytes
@@ -2209,13 +2212,15 @@ struct TnProb {          // 64 bytes
   int flags;             // 1: the direct epilogue adds the previous value of C (accumulate, nsplit == 1); 2: C / ldc allow 16-byte stores
 };
 struct GroupParams {
-  int count, nchunks, nsplit, mode;       // mode 0: fp32 atomics into C, 1: slabs, 2: direct (nsplit == 1)
-  long slab_stride;                        // floats between the slabs of consecutive K-splits
-  long k_per_split, K;
+  int count, nchunks, mode, pad_;          // mode of the chunks with more than one split: 0 fp32 atomics into C, 1 slabs
+  unsigned chunk_K[GROUP_MAX];             // tokens of the chunk's problems
+  int chunk_stride[GROUP_MAX];             // floats between this chunk's slabs of consecutive K-splits (mode 1)
+  unsigned short chunk_kps[GROUP_MAX];     // k-steps (of P4_BK tokens) per split
   unsigned short chunk_tiles[GROUP_MAX];
   unsigned char chunk_first[GROUP_MAX + 1];
+  unsigned char unit_first[GROUP_MAX + 1]; // unit = unit_first[chunk] + split; the chunk has unit_first[c + 1] - unit_first[c] splits
   unsigned char xcd_count[8];
-  unsigned char xcd_units[8][GROUP_XCD_UNITS];   // unit = split * nchunks + chunk
+  unsigned char xcd_units[8][GROUP_XCD_UNITS];
   TnProb p[GROUP_MAX];
 };
 static_assert(sizeof(GroupParams) <= 4000, "kernel arguments are limited to 4 KiB");
@@ -2229,8 +2234,9 @@ __global__ __launch_bounds__(P4_THREADS, 4) void gemm_bf16_p4_grouped_tn_kernel(
   for (;; ++j) {
     if (j >= nu) return;                       // this XCD's queue is shorter than the longest one (whole workgroup leaves)
     const int u = gp.xcd_units[xcd][j];
-    c = u % gp.nchunks;
-    split = u / gp.nchunks;
+    c = 0;
+    while (gp.unit_first[c + 1] <= u) ++c;     // (the host ends the table with the unit count: u < unit_first[nchunks])
+    split = u - gp.unit_first[c];
     const int tiles = gp.chunk_tiles[c];
     if (idx < tiles) break;
     idx -= tiles;
@@ -2240,24 +2246,28 @@ __global__ __launch_bounds__(P4_THREADS, 4) void gemm_bf16_p4_grouped_tn_kernel(
   i = __builtin_amdgcn_readfirstlane(i);              // (all of this is workgroup-uniform: keep it in SGPRs)
   idx = __builtin_amdgcn_readfirstlane(idx);
   split = __builtin_amdgcn_readfirstlane(split);
+  c = __builtin_amdgcn_readfirstlane(c);
   const TnProb& q = gp.p[i];
+  const int mode = gp.unit_first[c + 1] - gp.unit_first[c] == 1 ? 2 : gp.mode;   // 2: direct (this chunk has one split)
   KParams kp = {};
   kp.A = q.A; kp.B = q.B;
-  kp.M = q.M; kp.N = q.N; kp.K = gp.K;
+  kp.M = q.M; kp.N = q.N; kp.K = (long)gp.chunk_K[c];
   kp.lda = q.lda; kp.ldb = q.ldb; kp.ldc = q.ldc;
-  kp.k_per_split = gp.k_per_split;
+  kp.k_per_split = (long)gp.chunk_kps[c] * P4_BK;
   kp.batch_inner = 1;
   kp.a_vec = kp.b_vec = 1;
   kp.tiles_n = q.tiles_n; kp.ntiles = q.ntiles;
   kp.alpha = 1.0f; kp.drop_scale = 1.0f;
   kp.xcd_split = 1;
-  if (gp.mode == 1) {
-    // slab mode: this split's partial tile goes to its own slab with plain 16-byte stores (no atomics)
-    kp.C = q.C + (long)split * gp.slab_stride;
-    kp.a_rowsum = q.rowsum ? q.rowsum + (long)split * gp.slab_stride : nullptr;
+  if (mode == 1) {
+    // slab mode: this split's partial tile goes to its own slab with plain 16-byte stores (no atomics); q.C / q.rowsum
+    // are the problem's place in the chunk's slab 0 and q.ldc its dense row length
+    const long so = (long)split * gp.chunk_stride[c];
+    kp.C = q.C + so;
+    kp.a_rowsum = q.rowsum ? q.rowsum + so : nullptr;
     kp.c_vec = 1;
     kp.rowsum_store = 1;
-  } else if (gp.mode == 2) {
+  } else if (mode == 2) {
     // one split: the epilogue writes dW itself; an accumulating problem reads the previous value as a residual.
     // The bias gradient is ADDED to its destination by contract: one fp32 atomic per row (a single addend: exact)
     kp.C = q.C;
@@ -2279,14 +2289,14 @@ __global__ __launch_bounds__(P4_THREADS, 4) void gemm_bf16_p4_grouped_tn_kernel(
 // (a fixed summation order: weight gradients are bitwise reproducible, unlike fp32 atomics).
 struct ReduceSeg {       // 32 bytes
   float* dst;            // dW [rows, ld] or db [rows]
-  long off;              // offset of this segment inside a slab (floats)
+  unsigned off;          // offset of this segment inside its chunk's first slab, from the workspace's start (floats)
+  unsigned stride;       // floats between that chunk's slabs
   int rows, cols, ld;    // cols = the vector's length, rows = 1, ld = cols for a bias-gradient segment
-  int accumulate;
+  int acc_nsplit;        // bit 0: accumulate; the rest: the chunk's split count (segments of different chunks differ)
 };
 struct ReduceParams {
   const float* ws;
-  long slab_stride;
-  int nsplit, nseg;
+  int nseg, pad_;
   int blk_off[2 * GROUP_MAX + 1];   // first workgroup of every segment (a segment gets one workgroup per 2048 floats)
   ReduceSeg seg[2 * GROUP_MAX];
 };
@@ -2308,35 +2318,37 @@ __global__ __launch_bounds__(256) void grouped_reduce_kernel(ReduceParams rp) {
     if (q >= n4) break;
     const long e = 4 * q;
     const float* src = rp.ws + sg.off + e;
+    const int nsplit = sg.acc_nsplit >> 1, accumulate = sg.acc_nsplit & 1;
+    const long stride = (long)sg.stride;
     // slabs in groups of eight: the loads of a group are all in flight before the first add (with one load per
     // loop trip every slab was a round trip of its own: 3.0 TB/s at ViT-Base, where the 227 MB of slabs no longer
     // sit in the Infinity Cache); the additions keep the split order, so the result is bit-identical
     const long r = e / sg.cols, c = e - r * sg.cols;   // cols % 4 == 0 (or the segment is one contiguous vector)
     float* d = sg.dst + r * sg.ld + c;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sg.accumulate) o = *reinterpret_cast<const float4*>(d);
+    if (accumulate) o = *reinterpret_cast<const float4*>(d);
     float4 acc = *reinterpret_cast<const float4*>(src);
     int sidx = 1;
-    for (; sidx + 7 < rp.nsplit; sidx += 8) {
+    for (; sidx + 7 < nsplit; sidx += 8) {
       float4 v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(src + (long)(sidx + u) * rp.slab_stride);
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(src + (long)(sidx + u) * stride);
 #pragma unroll
       for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
     }
-    if (sidx + 6 < rp.nsplit) {                         // 7 left (8 splits)
+    if (sidx + 6 < nsplit) {                         // 7 left (8 splits)
       float4 v[7];
 #pragma unroll
-      for (int u = 0; u < 7; ++u) v[u] = *reinterpret_cast<const float4*>(src + (long)(sidx + u) * rp.slab_stride);
+      for (int u = 0; u < 7; ++u) v[u] = *reinterpret_cast<const float4*>(src + (long)(sidx + u) * stride);
 #pragma unroll
       for (int u = 0; u < 7; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
       sidx += 7;
     }
-    for (; sidx < rp.nsplit; ++sidx) {
-      const float4 v = *reinterpret_cast<const float4*>(src + (long)sidx * rp.slab_stride);
+    for (; sidx < nsplit; ++sidx) {
+      const float4 v = *reinterpret_cast<const float4*>(src + (long)sidx * stride);
       acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
-    if (sg.accumulate) { acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
+    if (accumulate) { acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w; }
     *reinterpret_cast<float4*>(d) = acc;
   }
 }
@@ -3232,21 +3244,15 @@ extern "C" int favit_gemm(const favit_gemm_t* g_in, void* stream) {
 
 namespace {
 
-// slab layout shared by the size query and the launch: per problem the dense [M, N] partial, then its [M] bias row
-long grouped_slab_floats(const favit_gemm_t* gs, int count) {
-  long tot = 0;
-  for (int i = 0; i < count; ++i) tot += gs[i].M * gs[i].N + ((gs[i].M + 3) / 4) * 4;
-  return (tot + 63) / 64 * 64;
-}
-
-// FAVIT_GROUPED_S=n (A/B measurements): force n K-splits.  Read once per process.
+// FAVIT_GROUPED_S=n (A/B measurements): force n K-splits (uniform groups).  Read once per process.
 int grouped_forced_splits() {
   static const int v = [] { const char* e = getenv("FAVIT_GROUPED_S"); return e ? atoi(e) : 0; }();
   return v;
 }
 
-// How a grouped launch is laid out: chunks (consecutive problems, <= 64 tiles), the number of K-splits and the
-// unit -> XCD queues.  The split count minimises
+// How a grouped launch is laid out: chunks (consecutive problems of one token count, <= 64 tiles), the number of
+// K-splits of every chunk and the unit -> XCD queues.  For a group with ONE token count (grouped_plan) every chunk gets
+// the same split count, the one that minimises
 //     max over XCDs of max(1, queue tiles / 64) x (k x 1.4 us x (1 + k / 4000) + 18 us)   k = 32-token k-steps per split
 //   + (nsplit > 1 ? (2 nsplit + 1) x output bytes / 5 TB/s + 5 us : 2 x output bytes / 5 TB/s)   slabs + reduction
 // among the split counts that keep a split at or below 6,400 tokens (when any does).  The constants are measured
@@ -3258,16 +3264,88 @@ int grouped_forced_splits() {
 // maximised slot utilisation alone and took 16 splits at ViT-Base; round 3 priced the slabs; round 4 adds the
 // multi-block launches, where one or two splits fill the chip at short token counts (cfg3: 12 blocks, no split, no
 // slabs, no reduction kernel: 19 us per block against 40).
+// Round 8, token counts that differ from chunk to chunk (grouped_plan_ragged): the same model with the same constants,
+// written per unit.  A unit of t tiles and k k-steps keeps its XCD's 64 slots busy for t / 64 x u(k), u(k) = k x 1.4 us
+// x (1 + k / 4000) + 18 us, and no queue finishes before its longest unit, so a queue costs
+//     max(max over its units of u(k), sum over its units of t / 64 x u(k))
+// -- for equal units that is the expression above.  Only chunks with more than one split pay slabs:
+//     sum over split chunks of (2 s_c + 1) x bytes_c / 5 TB/s + 5 us (once)  +  sum over the others of 2 x bytes_c / 5 TB/s.
+// The search starts from the fewest splits the 6,400-token cap allows and keeps splitting the chunk whose unit is the
+// most expensive while the modelled cost falls (it stops after six steps without a new minimum); units are packed
+// longest-first BY COST into the queue with the least cost, so a queue runs its long units first and the short
+// blocks fill the ends.  A launch of the cfg2 blocks of 5 .. 35 rows (40 .. 280 k-steps) comes out with the three short
+// blocks as one direct-writing unit each and the three long ones in two units; the whole pruned cfg2 encoder (5 .. 71
+// rows) with 25 units, three or four per queue, 1 .. 4 splits per block.
+// No new constant.  Measured (tools/grouped_probe.py ROWS=..., round 8, random data, back-to-back, launch + reduction):
+// the twelve cfg2 blocks in one launch 710 us against 758 block by block (modelled 727 + 87 of slabs); blocks 5 .. 35
+// 188 against 274 (modelled 221 + 35); 41 + 47 126 / 135; 53 + 59 149 / 160 -- 1.33 .. 1.57 us per k-step of a 512-slot
+// round all in, so the 1.4 us / 18 us pair still ranks the plans.  Inside the training step the same twelve-block launch
+// takes ~500 us + 40 of reduction where the per-block launches took 634 + 142: the model is
+// pessimistic for queues of several units there, which only makes it split a little more than needed.
 struct GroupPlan {
   int nchunks;
   int chunk_first[GROUP_MAX + 1];
   int chunk_tiles[GROUP_MAX];
-  long nsplit, kps;
+  long chunk_K[GROUP_MAX];
+  long chunk_nsplit[GROUP_MAX], chunk_kps[GROUP_MAX];      // kps in tokens
+  long chunk_out[GROUP_MAX];                                // sum of M x N over the chunk's problems (floats)
+  long chunk_floats[GROUP_MAX];                             // one slab of the chunk: partial tiles + bias rows (floats)
+  int unit_first[GROUP_MAX + 1];
+  long nsplit;                                              // the largest split count of the launch
   int xcd_count[8];
   int xcd_units[8][GROUP_XCD_UNITS];
   long max_queue_tiles;
 };
 
+// slab layout shared by the size query and the launch: per problem the dense [M, N] partial, then its [M] bias row
+long grouped_chunk_floats(const favit_gemm_t* gs, int first, int last) {
+  long tot = 0;
+  for (int i = first; i < last; ++i) tot += gs[i].M * gs[i].N + ((gs[i].M + 3) / 4) * 4;
+  return (tot + 63) / 64 * 64;
+}
+
+// workspace of a planned launch: only chunks with more than one split get slabs
+long grouped_ws_floats(const GroupPlan& pl) {
+  long tot = 0;
+  for (int c = 0; c < pl.nchunks; ++c)
+    if (pl.chunk_nsplit[c] > 1) tot += pl.chunk_nsplit[c] * pl.chunk_floats[c];
+  return tot;
+}
+
+// chunks: consecutive problems of one K with at most 64 tiles together
+bool grouped_chunks(const favit_gemm_t* gs, int count, GroupPlan& pl) {
+  pl.nchunks = 0;
+  int cur = 0;
+  for (int i = 0; i < count; ++i) {
+    const long t = ((gs[i].M + P4_BM - 1) / P4_BM) * ((gs[i].N + BN - 1) / BN);
+    if (t > 65535) return false;
+    if (pl.nchunks == 0 || cur + t > 64 || gs[i].K != pl.chunk_K[pl.nchunks - 1]) {
+      pl.chunk_first[pl.nchunks] = i;
+      pl.chunk_tiles[pl.nchunks] = 0;
+      pl.chunk_K[pl.nchunks] = gs[i].K;
+      pl.chunk_out[pl.nchunks] = 0;
+      ++pl.nchunks;
+      cur = 0;
+    }
+    cur += (int)t;
+    pl.chunk_tiles[pl.nchunks - 1] = cur;
+    pl.chunk_out[pl.nchunks - 1] += gs[i].M * gs[i].N;
+  }
+  pl.chunk_first[pl.nchunks] = count;
+  for (int c = 0; c < pl.nchunks; ++c) pl.chunk_floats[c] = grouped_chunk_floats(gs, pl.chunk_first[c], pl.chunk_first[c + 1]);
+  return true;
+}
+
+void grouped_unit_table(GroupPlan& pl) {
+  pl.unit_first[0] = 0;
+  pl.nsplit = 0;
+  for (int c = 0; c < pl.nchunks; ++c) {
+    pl.unit_first[c + 1] = pl.unit_first[c] + (int)pl.chunk_nsplit[c];
+    pl.nsplit = pl.chunk_nsplit[c] > pl.nsplit ? pl.chunk_nsplit[c] : pl.nsplit;
+  }
+}
+
+// One split count for every chunk (a group with one token count): the round-4 packing, by tiles.
 bool grouped_pack(GroupPlan& pl, long nsplit) {
   // longest-first packing of the units into eight queues (units of one chunk are equal: walk chunks by size)
   const int nunits = pl.nchunks * (int)nsplit;
@@ -3285,7 +3363,7 @@ bool grouped_pack(GroupPlan& pl, long nsplit) {
       for (int x = 0; x < 8; ++x)
         if (pl.xcd_count[x] < GROUP_XCD_UNITS && (best < 0 || load[x] < load[best])) best = x;
       if (best < 0) return false;
-      pl.xcd_units[best][pl.xcd_count[best]++] = (int)(sp * pl.nchunks + c);
+      pl.xcd_units[best][pl.xcd_count[best]++] = (int)(c * nsplit + sp);
       load[best] += pl.chunk_tiles[c];
     }
   }
@@ -3297,23 +3375,9 @@ bool grouped_pack(GroupPlan& pl, long nsplit) {
 // Returns false if the problems cannot be grouped (more than GROUP_MAX chunks cannot happen: a chunk holds >= 1 problem).
 bool grouped_plan(const favit_gemm_t* gs, int count, GroupPlan& pl) {
   const long K = gs[0].K;
-  pl.nchunks = 0;
+  if (!grouped_chunks(gs, count, pl)) return false;
   long out_floats = 0;
-  int cur = 0;
-  for (int i = 0; i < count; ++i) {
-    const long t = ((gs[i].M + P4_BM - 1) / P4_BM) * ((gs[i].N + BN - 1) / BN);
-    if (t > 65535) return false;
-    out_floats += gs[i].M * gs[i].N;
-    if (pl.nchunks == 0 || cur + t > 64) {
-      pl.chunk_first[pl.nchunks] = i;
-      pl.chunk_tiles[pl.nchunks] = 0;
-      ++pl.nchunks;
-      cur = 0;
-    }
-    cur += (int)t;
-    pl.chunk_tiles[pl.nchunks - 1] = cur;
-  }
-  pl.chunk_first[pl.nchunks] = count;
+  for (int c = 0; c < pl.nchunks; ++c) out_floats += pl.chunk_out[c];
   static const long cand[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
   const int forced = grouped_forced_splits();
   double best = 0.0;
@@ -3325,6 +3389,7 @@ bool grouped_plan(const favit_gemm_t* gs, int count, GroupPlan& pl) {
     long kps = (K + s - 1) / s;
     kps = ((kps + P4_BK - 1) / P4_BK) * P4_BK;
     if (s > 1 && (s - 1) * kps >= K) continue;        // the last split would be empty
+    if (kps / P4_BK > 65535) continue;                // (GroupParams keeps the k-steps of a split in 16 bits)
     GroupPlan trial = pl;
     if (!grouped_pack(trial, s)) continue;
     // (tiles of a queue do not run in strict rounds: 216 tiles on 64 slots take ~3.4 tile times, not 4)
@@ -3340,24 +3405,145 @@ bool grouped_plan(const favit_gemm_t* gs, int count, GroupPlan& pl) {
     if (forced > 0) break;
   }
   if (best_s == 0) return false;
-  pl.nsplit = best_s;
-  pl.kps = best_kps;
+  for (int c = 0; c < pl.nchunks; ++c) { pl.chunk_nsplit[c] = best_s; pl.chunk_kps[c] = best_kps; }
+  grouped_unit_table(pl);
   return grouped_pack(pl, best_s);
 }
 
-int grouped_tn_impl(const favit_gemm_t* gs, int32_t count, float* ws, int64_t ws_bytes, void* stream) {
+// tokens per split of K tokens in s splits, or 0 if the last split would be empty
+long grouped_kps(long K, long s) {
+  long kps = (K + s - 1) / s;
+  kps = ((kps + P4_BK - 1) / P4_BK) * P4_BK;
+  if (s > 1 && (s - 1) * kps >= K) return 0;
+  return kps;
+}
+
+double grouped_unit_time(long kps) {
+  const double k = (double)(kps / P4_BK);
+  return k * 1.4e-6 * (1.0 + k / 4000.0) + 18.0e-6;
+}
+
+// Per-chunk split counts -> queues (longest-first by cost, tiles x unit time) and the modelled time of the launch.
+bool grouped_pack_ragged(GroupPlan& pl, double* cost_out) {
+  grouped_unit_table(pl);
+  const int nunits = pl.unit_first[pl.nchunks];
+  if (nunits > 255 || nunits > 8 * GROUP_XCD_UNITS) return false;
+  int order[GROUP_MAX];                              // the units of a chunk are equal: sort the chunks
+  double ut[GROUP_MAX], uc[GROUP_MAX];
+  for (int c = 0; c < pl.nchunks; ++c) {
+    order[c] = c;
+    ut[c] = grouped_unit_time(pl.chunk_kps[c]);
+    uc[c] = (double)pl.chunk_tiles[c] / 64.0 * ut[c];
+  }
+  for (int a = 1; a < pl.nchunks; ++a)            // insertion sort, descending cost (stable)
+    for (int b = a; b > 0 && uc[order[b]] > uc[order[b - 1]]; --b) { int t = order[b]; order[b] = order[b - 1]; order[b - 1] = t; }
+  double load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, longest[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int x = 0; x < 8; ++x) pl.xcd_count[x] = 0;
+  for (int oc = 0; oc < pl.nchunks; ++oc) {
+    const int c = order[oc];
+    for (long sp = 0; sp < pl.chunk_nsplit[c]; ++sp) {
+      int best = -1;
+      for (int x = 0; x < 8; ++x)
+        if (pl.xcd_count[x] < GROUP_XCD_UNITS && (best < 0 || load[x] < load[best])) best = x;
+      if (best < 0) return false;
+      pl.xcd_units[best][pl.xcd_count[best]++] = pl.unit_first[c] + (int)sp;
+      load[best] += uc[c];
+      tiles[best] += pl.chunk_tiles[c];
+      longest[best] = ut[c] > longest[best] ? ut[c] : longest[best];
+    }
+  }
+  pl.max_queue_tiles = 0;
+  double t = 0.0;
+  for (int x = 0; x < 8; ++x) {
+    pl.max_queue_tiles = tiles[x] > pl.max_queue_tiles ? tiles[x] : pl.max_queue_tiles;
+    const double q = load[x] > longest[x] ? load[x] : longest[x];
+    t = q > t ? q : t;
+  }
+  bool any_split = false;
+  for (int c = 0; c < pl.nchunks; ++c) {
+    const double bytes = 4.0 * (double)pl.chunk_out[c];
+    if (pl.chunk_nsplit[c] > 1) { t += (2.0 * (double)pl.chunk_nsplit[c] + 1.0) * bytes / 5.0e12; any_split = true; }
+    else t += 2.0 * bytes / 5.0e12;
+  }
+  if (cost_out) *cost_out = t + (any_split ? 5.0e-6 : 0.0);
+  return true;
+}
+
+// Token counts that differ from chunk to chunk.  A group with one token count gets grouped_plan's plan.
+bool grouped_plan_ragged(const favit_gemm_t* gs, int count, GroupPlan& pl) {
+  bool uniform = true;
+  for (int i = 1; i < count; ++i) uniform = uniform && gs[i].K == gs[0].K;
+  if (uniform) return grouped_plan(gs, count, pl);
+  // (the size query and the launch plan the same list one after the other: remember the last plan of this thread)
+  struct Memo { int count = 0; long sig[3 * GROUP_MAX]; GroupPlan pl; };
+  thread_local Memo memo;
+  long sig[3 * GROUP_MAX];
+  for (int i = 0; i < count; ++i) { sig[3 * i] = gs[i].M; sig[3 * i + 1] = gs[i].N; sig[3 * i + 2] = gs[i].K; }
+  if (memo.count == count && memcmp(memo.sig, sig, sizeof(long) * 3 * (size_t)count) == 0) { pl = memo.pl; return true; }
+  if (!grouped_chunks(gs, count, pl)) return false;
+  constexpr long KPS_CAP = 6400, S_MAX = 32;
+  auto next_valid = [&](int c, long s) -> long {     // the smallest usable split count >= s, or 0
+    for (; s <= S_MAX; ++s) {
+      const long kps = grouped_kps(pl.chunk_K[c], s);
+      if (kps > 0 && kps / P4_BK <= 65535) return s;
+    }
+    return 0;
+  };
+  for (int c = 0; c < pl.nchunks; ++c) {
+    long s = next_valid(c, (pl.chunk_K[c] + KPS_CAP - 1) / KPS_CAP);
+    if (s == 0) s = next_valid(c, 1);                // (the cap cannot be kept: as few splits as the format takes)
+    if (s == 0) return false;
+    pl.chunk_nsplit[c] = s;
+    pl.chunk_kps[c] = grouped_kps(pl.chunk_K[c], s);
+  }
+  GroupPlan best;
+  double best_cost = 0.0;
+  bool have = false;
+  int stale = 0;
+  for (;;) {
+    double cost = 0.0;
+    GroupPlan trial = pl;
+    if (grouped_pack_ragged(trial, &cost)) {
+      if (!have || cost < best_cost) { best = trial; best_cost = cost; have = true; stale = 0; }
+      else if (++stale >= 6) break;
+    } else if (have) break;                          // (more units only make the packing harder)
+    // split the chunk whose unit is the most expensive once more
+    int pick = -1;
+    long pick_s = 0;
+    double pick_cost = 0.0;
+    for (int c = 0; c < pl.nchunks; ++c) {
+      const long s = next_valid(c, pl.chunk_nsplit[c] + 1);
+      if (s == 0) continue;
+      const double uc = (double)pl.chunk_tiles[c] * grouped_unit_time(pl.chunk_kps[c]);
+      if (pick < 0 || uc > pick_cost) { pick = c; pick_s = s; pick_cost = uc; }
+    }
+    if (pick < 0) break;
+    pl.chunk_nsplit[pick] = pick_s;
+    pl.chunk_kps[pick] = grouped_kps(pl.chunk_K[pick], pick_s);
+  }
+  if (!have) return false;
+  pl = best;
+  memo.count = count;
+  memcpy(memo.sig, sig, sizeof(long) * 3 * (size_t)count);
+  memo.pl = pl;
+  return true;
+}
+
+// ragged: token counts may differ between chunks and the caller's contract is strict (a workspace smaller than the
+// query's answer is refused); otherwise today's uniform launch, which falls back to fp32 atomics without a workspace.
+int grouped_tn_impl(const favit_gemm_t* gs, int32_t count, float* ws, int64_t ws_bytes, void* stream, bool ragged) {
   if (!gs || count <= 0 || count > GROUP_MAX) return FAVIT_ERR_INVALID;
   hipStream_t st = as_stream(stream);
   GroupParams gp;
   memset(&gp, 0, sizeof(gp));          // every field defined, whatever is added to the structs later
   gp.count = count;
   const long K = gs[0].K;
-  if (K <= 0 || (K % P4_BK) != 0) return FAVIT_ERR_UNSUPPORTED;
-  bool direct_ok = true;               // nsplit == 1 needs nothing; 16-byte stores when C allows them
   for (int i = 0; i < count; ++i) {
     const favit_gemm_t* g = gs + i;
     if (!g->A || !g->B || !g->C || g->M <= 0 || g->N <= 0) return FAVIT_ERR_INVALID;
-    if (g->K != K || g->in_dtype != FAVIT_BF16 || g->out_dtype != FAVIT_F32 || g->a_kmajor || g->b_kmajor ||
+    if (g->K <= 0 || (g->K % P4_BK) != 0 || g->K > (long)UINT32_MAX || (!ragged && g->K != K)) return FAVIT_ERR_UNSUPPORTED;
+    if (g->in_dtype != FAVIT_BF16 || g->out_dtype != FAVIT_F32 || g->a_kmajor || g->b_kmajor ||
         (g->batch > 1) || g->act != FAVIT_ACT_NONE || g->aux_in || g->aux_out || g->residual || g->bias ||
         g->dropout_p > 0.f || g->alpha != 1.0f)
       return FAVIT_ERR_UNSUPPORTED;
@@ -3372,63 +3558,82 @@ int grouped_tn_impl(const favit_gemm_t* gs, int32_t count, float* ws, int64_t ws
     q.ntiles = (int)(((g->M + P4_BM - 1) / P4_BM) * q.tiles_n);
     q.flags = (g->accumulate ? 1 : 0) | (((g->ldc % 4) == 0 && aligned(g->C, 16)) ? 2 : 0);
   }
-  const long stride = grouped_slab_floats(gs, count);
   bool slab_dst_ok = ws != nullptr && aligned(ws, 16);
   for (int i = 0; i < count; ++i)      // the reduction writes 16-byte vectors: unaligned destinations keep the atomic path
     slab_dst_ok = slab_dst_ok && (gs[i].ldc % 4) == 0 && aligned(gs[i].C, 16) && (!gs[i].a_rowsum || aligned(gs[i].a_rowsum, 16));
   GroupPlan pl;
-  if (!grouped_plan(gs, count, pl)) return FAVIT_ERR_UNSUPPORTED;
+  if (!(ragged ? grouped_plan_ragged(gs, count, pl) : grouped_plan(gs, count, pl))) return FAVIT_ERR_UNSUPPORTED;
   const long nsplit = pl.nsplit;
-  gp.nsplit = (int)nsplit;
-  gp.k_per_split = pl.kps;
-  gp.K = K;
+  const long ws_floats = grouped_ws_floats(pl);
+  if (ws_floats > (long)UINT32_MAX) return FAVIT_ERR_UNSUPPORTED;      // (the reduction keeps slab offsets in 32 bits)
+  for (int c = 0; c < pl.nchunks; ++c)
+    if (pl.chunk_floats[c] > INT32_MAX) return FAVIT_ERR_UNSUPPORTED;
+  if (ragged && ws != nullptr && ws_bytes < (int64_t)(ws_floats * 4)) return FAVIT_ERR_INVALID;
   gp.nchunks = pl.nchunks;
-  for (int c = 0; c < pl.nchunks; ++c) { gp.chunk_tiles[c] = (unsigned short)pl.chunk_tiles[c]; gp.chunk_first[c] = (unsigned char)pl.chunk_first[c]; }
+  for (int c = 0; c < pl.nchunks; ++c) {
+    gp.chunk_tiles[c] = (unsigned short)pl.chunk_tiles[c];
+    gp.chunk_first[c] = (unsigned char)pl.chunk_first[c];
+    gp.unit_first[c] = (unsigned char)pl.unit_first[c];
+    gp.chunk_K[c] = (unsigned)pl.chunk_K[c];
+    gp.chunk_kps[c] = (unsigned short)(pl.chunk_kps[c] / P4_BK);
+  }
   gp.chunk_first[pl.nchunks] = (unsigned char)count;
+  gp.unit_first[pl.nchunks] = (unsigned char)pl.unit_first[pl.nchunks];
   for (int x = 0; x < 8; ++x) {
     gp.xcd_count[x] = (unsigned char)pl.xcd_count[x];
     for (int j = 0; j < pl.xcd_count[x]; ++j) gp.xcd_units[x][j] = (unsigned char)pl.xcd_units[x][j];
   }
-  const bool slabs = nsplit > 1 && slab_dst_ok && ws_bytes >= (int64_t)(nsplit * stride * 4);
-  gp.mode = nsplit == 1 ? 2 : (slabs ? 1 : 0);
-  gp.slab_stride = slabs ? stride : 0;
+  const bool slabs = nsplit > 1 && slab_dst_ok && ws_bytes >= (int64_t)(ws_floats * 4);
+  gp.mode = slabs ? 1 : 0;             // (of the chunks with more than one split; a chunk with one split writes dW itself)
   ReduceParams rp;
   if (slabs) {
     // Every split writes its partial tiles with plain 16-byte stores into its own slab; a second kernel adds the
     // slabs in split order.  fp32 atomics reach ~1.3 TB/s chip-wide (MI355X_MICROARCH.md) against ~5 TB/s for plain
     // stores + the reduction's reads: measured 318 -> 227 us main loop + epilogue at the cfg2 block shapes and
     // 914 -> 538 us at ViT-Base (tools/grouped_probe.py), and the result no longer depends on arrival order.
+    // The workspace holds, chunk after chunk, the slabs of the chunks that are split.
     memset(&rp, 0, sizeof(rp));
-    rp.ws = ws; rp.slab_stride = stride; rp.nsplit = (int)nsplit; rp.nseg = 0;
-    long o = 0;
+    rp.ws = ws; rp.nseg = 0;
+    long base = 0;
     int blk = 0;
-    auto add_seg = [&](float* dst, long off, long rows, long cols, long ld, int acc) {
-      rp.seg[rp.nseg] = ReduceSeg{dst, off, (int)rows, (int)cols, (int)ld, acc};
-      rp.blk_off[rp.nseg++] = blk;
-      blk += (int)((rows * cols / 4 + 256 * REDUCE_PER_BLOCK - 1) / (256 * REDUCE_PER_BLOCK));
-    };
-    for (int i = 0; i < count; ++i) {
-      TnProb& q = gp.p[i];
-      add_seg(reinterpret_cast<float*>(gs[i].C), o, gs[i].M, gs[i].N, gs[i].ldc, gs[i].accumulate ? 1 : 0);
-      q.C = ws + o;
-      q.ldc = (int)gs[i].N;
-      o += gs[i].M * gs[i].N;
-      if (gs[i].a_rowsum) {
-        // the bias gradient is always ADDED to its destination (the fused column sum's contract); M % 8 == 0
-        add_seg(gs[i].a_rowsum, o, 1, gs[i].M, gs[i].M, 1);
-        q.rowsum = ws + o;
+    for (int c = 0; c < pl.nchunks; ++c) {
+      const long sc = pl.chunk_nsplit[c];
+      if (sc <= 1) continue;
+      const long stride = pl.chunk_floats[c];
+      gp.chunk_stride[c] = (int)stride;
+      long o = base;
+      auto add_seg = [&](float* dst, long off, long rows, long cols, long ld, int acc) {
+        rp.seg[rp.nseg] = ReduceSeg{dst, (unsigned)off, (unsigned)stride, (int)rows, (int)cols, (int)ld, acc | ((int)sc << 1)};
+        rp.blk_off[rp.nseg++] = blk;
+        blk += (int)((rows * cols / 4 + 256 * REDUCE_PER_BLOCK - 1) / (256 * REDUCE_PER_BLOCK));
+      };
+      for (int i = pl.chunk_first[c]; i < pl.chunk_first[c + 1]; ++i) {
+        TnProb& q = gp.p[i];
+        add_seg(reinterpret_cast<float*>(gs[i].C), o, gs[i].M, gs[i].N, gs[i].ldc, gs[i].accumulate ? 1 : 0);
+        q.C = ws + o;
+        q.ldc = (int)gs[i].N;
+        o += gs[i].M * gs[i].N;
+        if (gs[i].a_rowsum) {
+          // the bias gradient is always ADDED to its destination (the fused column sum's contract); M % 8 == 0
+          add_seg(gs[i].a_rowsum, o, 1, gs[i].M, gs[i].M, 1);
+          q.rowsum = ws + o;
+        }
+        o += ((gs[i].M + 3) / 4) * 4;
       }
-      o += ((gs[i].M + 3) / 4) * 4;
+      base += sc * stride;
     }
     rp.blk_off[rp.nseg] = blk;
-  } else if (gp.mode == 0) {
-    for (int i = 0; i < count; ++i) {
-      if (!gs[i].accumulate) {
-        const long total = gs[i].M * gs[i].N;
-        const int zb = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-        hipLaunchKernelGGL(zero_c_kernel, dim3(zb, 1, 1), dim3(256), 0, st, reinterpret_cast<float*>(gs[i].C), gs[i].M,
-                           gs[i].N, gs[i].ldc, 0L, 0L, 1);
-        FAVIT_CHECK_LAUNCH();
+  } else if (nsplit > 1) {
+    for (int c = 0; c < pl.nchunks; ++c) {
+      if (pl.chunk_nsplit[c] <= 1) continue;
+      for (int i = pl.chunk_first[c]; i < pl.chunk_first[c + 1]; ++i) {
+        if (!gs[i].accumulate) {
+          const long total = gs[i].M * gs[i].N;
+          const int zb = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+          hipLaunchKernelGGL(zero_c_kernel, dim3(zb, 1, 1), dim3(256), 0, st, reinterpret_cast<float*>(gs[i].C), gs[i].M,
+                             gs[i].N, gs[i].ldc, 0L, 0L, 1);
+          FAVIT_CHECK_LAUNCH();
+        }
       }
     }
   }
@@ -3447,25 +3652,73 @@ int grouped_tn_impl(const favit_gemm_t* gs, int32_t count, float* ws, int64_t ws
   return FAVIT_OK;
 }
 
+int64_t grouped_ws_query(const favit_gemm_t* gs, int32_t count, bool ragged) {
+  if (!gs || count <= 0 || count > GROUP_MAX) return 0;
+  for (int i = 0; i < count; ++i)
+    if (gs[i].K <= 0 || gs[i].M <= 0 || gs[i].N <= 0 || (ragged ? (gs[i].K % P4_BK) != 0 : gs[i].K != gs[0].K)) return 0;
+  GroupPlan pl;
+  if (!(ragged ? grouped_plan_ragged(gs, count, pl) : grouped_plan(gs, count, pl))) return 0;
+  return (int64_t)(grouped_ws_floats(pl) * 4);
+}
+
 }  // namespace
 
 extern "C" int favit_gemm_grouped_tn(const favit_gemm_t* gs, int32_t count, void* stream) {
-  return grouped_tn_impl(gs, count, nullptr, 0, stream);
+  return grouped_tn_impl(gs, count, nullptr, 0, stream, false);
 }
 
 extern "C" int64_t favit_gemm_grouped_tn_workspace(const favit_gemm_t* gs, int32_t count) {
-  if (!gs || count <= 0 || count > GROUP_MAX || gs[0].K <= 0) return 0;
-  GroupPlan pl;
-  if (!grouped_plan(gs, count, pl)) return 0;
-  return pl.nsplit > 1 ? (int64_t)(pl.nsplit * grouped_slab_floats(gs, count) * 4) : 0;
+  return grouped_ws_query(gs, count, false);
 }
 
 extern "C" int favit_gemm_grouped_tn_ws(const favit_gemm_t* gs, int32_t count, void* workspace, int64_t workspace_bytes,
                                         void* stream) {
-  return grouped_tn_impl(gs, count, reinterpret_cast<float*>(workspace), workspace_bytes, stream);
+  return grouped_tn_impl(gs, count, reinterpret_cast<float*>(workspace), workspace_bytes, stream, false);
+}
+
+extern "C" int favit_gemm_grouped_tn_ragged(const favit_gemm_t* gs, int32_t count, void* stream) {
+  return grouped_tn_impl(gs, count, nullptr, 0, stream, true);
+}
+
+extern "C" int64_t favit_gemm_grouped_tn_ragged_workspace(const favit_gemm_t* gs, int32_t count) {
+  return grouped_ws_query(gs, count, true);
+}
+
+extern "C" int favit_gemm_grouped_tn_ragged_ws(const favit_gemm_t* gs, int32_t count, void* workspace,
+                                               int64_t workspace_bytes, void* stream) {
+  if (!workspace && workspace_bytes > 0) return FAVIT_ERR_INVALID;
+  return grouped_tn_impl(gs, count, reinterpret_cast<float*>(workspace), workspace_bytes, stream, true);
 }
 
 extern "C" int favit_gemm_grouped_last_splits(void) { return g_last_grouped_splits; }
+
+// Diagnostic (host only, nothing is launched): the plan a grouped launch of these problems would get, as numbers --
+// out = {nchunks, units, longest queue in tiles, workspace bytes}, per chunk {first problem, tiles, K, splits, tokens
+// per split}, per XCD queue {units, unit ids ...} (unit id = sum of the splits of the chunks before + split).
+// Returns the number of values written, or a negative FAVIT_ERR_*.
+extern "C" int favit_gemm_grouped_plan(const favit_gemm_t* gs, int32_t count, int32_t ragged, int64_t* out, int32_t cap) {
+  if (!gs || !out || count <= 0 || count > GROUP_MAX) return FAVIT_ERR_INVALID;
+  for (int i = 0; i < count; ++i) {
+    if (gs[i].M <= 0 || gs[i].N <= 0) return FAVIT_ERR_INVALID;
+    if (gs[i].K <= 0 || (gs[i].K % P4_BK) != 0 || (!ragged && gs[i].K != gs[0].K)) return FAVIT_ERR_UNSUPPORTED;
+  }
+  GroupPlan pl;
+  if (!(ragged ? grouped_plan_ragged(gs, count, pl) : grouped_plan(gs, count, pl))) return FAVIT_ERR_UNSUPPORTED;
+  int need = 4 + 5 * pl.nchunks + 8;
+  for (int x = 0; x < 8; ++x) need += pl.xcd_count[x];
+  if (need > cap) return FAVIT_ERR_INVALID;
+  int o = 0;
+  out[o++] = pl.nchunks; out[o++] = pl.unit_first[pl.nchunks]; out[o++] = pl.max_queue_tiles; out[o++] = grouped_ws_floats(pl) * 4;
+  for (int c = 0; c < pl.nchunks; ++c) {
+    out[o++] = pl.chunk_first[c]; out[o++] = pl.chunk_tiles[c]; out[o++] = pl.chunk_K[c];
+    out[o++] = pl.chunk_nsplit[c]; out[o++] = pl.chunk_kps[c];
+  }
+  for (int x = 0; x < 8; ++x) {
+    out[o++] = pl.xcd_count[x];
+    for (int j = 0; j < pl.xcd_count[x]; ++j) out[o++] = pl.xcd_units[x][j];
+  }
+  return o;
+}
 
 // LayerNorm + small-M forward GEMM in one launch (gemm_bf16_s64ln_kernel); see include/favit.h.
 extern "C" int favit_ln_gemm(const favit_gemm_t* g, const float* x, int64_t ldx, const float* gamma, const float* beta,

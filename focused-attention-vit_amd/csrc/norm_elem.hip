@@ -3,6 +3,7 @@
 // cross-entropy (plain / label-smoothed), global gradient norm and AdamW (plain / clipped).  All are one-pass, 16-B-per-lane coalesced; LayerNorm keeps
 // the row in registers (one 64-lane wave per token row, shuffle reductions).
 #include "common.h"
+#include <string.h>
 
 extern "C" unsigned* favit_health_ptr_(void);
 
@@ -344,6 +345,48 @@ __global__ __launch_bounds__(1024) void reduce_rows_multi_kernel(ReduceMulti rm,
   const int col = blockIdx.x * 64 + cx;
   const float* src = rm.in[e] + (long)blockIdx.y * rows * cols;
   float* dst = blockIdx.y ? rm.out1[e] : rm.out0[e];
+  const long per = (rows + zsplit - 1) / zsplit;
+  const long rbeg = (long)z * per, rend = min(rows, rbeg + per);
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  if (col < cols) {
+    long r = rbeg + ry;
+    for (; r + 48 < rend; r += 64) {
+      s0 += src[r * cols + col];
+      s1 += src[(r + 16) * cols + col];
+      s2 += src[(r + 32) * cols + col];
+      s3 += src[(r + 48) * cols + col];
+    }
+    for (; r < rend; r += 16) s0 += src[r * cols + col];
+  }
+  red[ry][cx] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  if (ry == 0 && col < cols) {
+    float t = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) t += red[q][cx];
+    atomicAdd(dst + col, t);
+  }
+}
+
+// The same for entries whose row counts differ (the partial sums of a pruned encoder: every block has its own row
+// count, so the one-shape launch above ran once per shape -- 6 launches per cfg2 step).  Entry e keeps the row split
+// it has alone, rows >= 512 ? 8 : 1, and the summation order inside a split, so its result is what the one-shape
+// launch gives; blockIdx.z walks the (entry, split) pairs, zoff[e] = first z of entry e.
+struct ReduceMultiRagged {
+  ReduceMulti rm;
+  int rows[REDUCE_MULTI_MAX];
+  unsigned short zoff[REDUCE_MULTI_MAX + 1];
+};
+__global__ __launch_bounds__(1024) void reduce_rows_multi_ragged_kernel(ReduceMultiRagged rr, int n, int cols) {
+  __shared__ float red[16][64];
+  int e = 0;
+  while (e + 1 < n && rr.zoff[e + 1] <= blockIdx.z) ++e;       // (workgroup-uniform, at most 31 steps)
+  const int zsplit = rr.zoff[e + 1] - rr.zoff[e], z = blockIdx.z - rr.zoff[e];
+  const long rows = rr.rows[e];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + cx;
+  const float* src = rr.rm.in[e] + (long)blockIdx.y * rows * cols;
+  float* dst = blockIdx.y ? rr.rm.out1[e] : rr.rm.out0[e];
   const long per = (rows + zsplit - 1) / zsplit;
   const long rbeg = (long)z * per, rend = min(rows, rbeg + per);
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -1078,6 +1121,26 @@ extern "C" int favit_reduce_rows_multi(int32_t n, const float* const* in, float*
   const int zsplit = rows >= 512 ? 8 : 1;
   hipLaunchKernelGGL(reduce_rows_multi_kernel, dim3((cols + 63) / 64, 2, (unsigned)(n * zsplit)), dim3(1024), 0,
                      as_stream(stream), rm, (long)rows, cols, zsplit);
+  FAVIT_CHECK_LAUNCH();
+  return FAVIT_OK;
+}
+
+extern "C" int favit_reduce_rows_multi_ragged(int32_t n, const float* const* in, float* const* out0, float* const* out1,
+                                              const int64_t* rows, int32_t cols, void* stream) {
+  if (n <= 0 || n > REDUCE_MULTI_MAX || !in || !out0 || !out1 || !rows || cols <= 0) return FAVIT_ERR_INVALID;
+  ReduceMultiRagged rr;
+  memset(&rr, 0, sizeof(rr));
+  int z = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!in[i] || !out0[i] || !out1[i] || rows[i] <= 0 || rows[i] > INT32_MAX) return FAVIT_ERR_INVALID;
+    rr.rm.in[i] = in[i]; rr.rm.out0[i] = out0[i]; rr.rm.out1[i] = out1[i];
+    rr.rows[i] = (int)rows[i];
+    rr.zoff[i] = (unsigned short)z;
+    z += rows[i] >= 512 ? 8 : 1;
+  }
+  rr.zoff[n] = (unsigned short)z;
+  hipLaunchKernelGGL(reduce_rows_multi_ragged_kernel, dim3((cols + 63) / 64, 2, (unsigned)z), dim3(1024), 0,
+                     as_stream(stream), rr, (int)n, cols);
   FAVIT_CHECK_LAUNCH();
   return FAVIT_OK;
 }

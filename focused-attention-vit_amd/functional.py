@@ -482,28 +482,47 @@ def lin_bwd_x(dy, w_c, M, N, Kd, out_dtype, *, dgelu_pre=None, pre_is_grad=False
 # and the more tiles it holds, the fewer K-splits it needs to fill the chip (round 4; csrc/gemm.hip grouped_plan: the
 # twelve blocks of cfg3 in ONE launch without any split, slab or reduction kernel: 19 us per block against 40).
 # How long it waits is bounded by the bytes the waiting operands keep alive (FAVIT_WGRAD_HOLD_MB, default 384: about
-# the Infinity Cache + L2): at 50,432 tokens one block already holds 620 MB, so cfg2 / cfg4 launch per block as
-# before -- measured, four cfg2 blocks per launch make the launch itself 2.5 % faster and the STEP 1 % slower
+# the Infinity Cache + L2): at 50,432 tokens one block already holds 620 MB, so the dense cfg2 / cfg4 step launches per
+# block as before -- measured, four cfg2 blocks per launch make the launch itself 2.5 % faster and the STEP 1 % slower
 # (14.49 vs 14.35 ms; cfg4 28.99 vs 28.82): the held dY buffers are no longer recycled block after block, every
 # input-gradient GEMM writes into memory that is cold in the Infinity Cache and the TLB (those GEMMs: 3.74 -> 3.84 ms).
 # At most four blocks per launch when somebody listens for finished gradients (data parallelism: the buckets of those
 # blocks go out while the rest of backward runs; the graph segments of train.GraphedStep end a launch as well).
-_WG = {"list": None, "blocks": 0, "every": 1, "bytes": 0}
+# A pruned (CLS-only) encoder has a different token count in every block.  Until round 8 a grouped launch shared one
+# token count and such an encoder launched per block; favit_gemm_grouped_tn_ragged plans K-splits per block, so its
+# blocks join one list under the same limits ("ragged").  The blocks grow as backward walks down (5 .. 71 rows at cfg2),
+# so the list is launched BEFORE the next block would pass a limit: EncoderOp.bwd tells flush_wgrads how many rows the
+# next block has.  "ends" are the list lengths at the block boundaries: if the library declines a ragged list, it is
+# launched block by block as before (then GEMM by GEMM), never half of it.
+_WG = {"list": None, "blocks": 0, "every": 1, "bytes": 0, "ragged": False, "ends": [], "blk_bytes": 0}
 _WG_HOLD_BYTES = int(float(os.environ.get("FAVIT_WGRAD_HOLD_MB", "384")) * (1 << 20))
+# (ragged lists wait longer by default: the pruned cfg2 encoder holds 1.4 GB in all and its step is fastest with ONE
+# launch for the twelve blocks -- DESIGN.md section 11 has the A/B; FAVIT_WGRAD_HOLD_MB sets both limits)
+_WG_HOLD_RAGGED_BYTES = int(float(os.environ.get("FAVIT_WGRAD_HOLD_MB", "2048")) * (1 << 20))
 
 
 def begin_wgrads(per_block: bool = False) -> None:
-    """per_block: the token count differs from block to block (CLS-only encoders) and a grouped launch shares it, so
-    there is nothing to group across blocks."""
+    """per_block: the token count differs from block to block (CLS-only encoders).  The blocks are grouped through the
+    ragged launch; in side-stream mode and with FAVIT_WGRAD_PER_BLOCK set every block launches on its own."""
     every = 4 if _STATE["grad_ready"] is not None else K.GROUP_MAX // 4
-    if per_block or _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
+    ragged = per_block
+    if _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
         every = 1                             # (side-stream mode and the A/B switch: one launch per block, as in round 3)
-    _WG.update(list=[], blocks=0, every=every, bytes=0)
+        ragged = False
+    _WG.update(list=[], blocks=0, every=every, bytes=0, ragged=ragged, ends=[], blk_bytes=0)
 
 
-def flush_wgrads(force: bool = True) -> bool:
+def _launch_wgrads(probs) -> None:
+    if not K.gemm_grouped_tn(probs):           # (one problem too: fine-tuning with frozen layers leaves only dWeff)
+        for dy, a, dw, db, acc in probs:
+            K.gemm(dy, a, dw, dy.shape[1], a.shape[1], dy.shape[0], dy.stride(0), a.stride(0), dw.stride(0),
+                   a_kmajor=False, b_kmajor=False, a_rowsum=db, accumulate=acc)
+
+
+def flush_wgrads(force: bool = True, next_rows=None) -> bool:
     """Launch the collected weight-gradient GEMMs (grouped if the library can, else one by one).  force=False: called
     at the end of a block -- launches only every `every` blocks or once the waiting operands exceed the hold limit.
+    next_rows = (rows of the block that just ended, rows of the next one) where the blocks differ (ragged lists).
     Returns True if the list is empty afterwards."""
     lst = _WG["list"]
     if lst is None:
@@ -511,19 +530,33 @@ def flush_wgrads(force: bool = True) -> bool:
     if not force:
         _WG["blocks"] += 1
         nb = _WG["blocks"]
+        if _WG["ragged"]:
+            ends = _WG["ends"]
+            n_blk = len(lst) - (ends[-1] if ends else 0)
+            b_blk = _WG["bytes"] - _WG["blk_bytes"]
+            ends.append(len(lst))
+            _WG["blk_bytes"] = _WG["bytes"]
+            # (would the NEXT block still fit the hold limit and the launch?  its operands scale with its rows)
+            scale = next_rows[1] / max(next_rows[0], 1) if next_rows else 1.0
+            if nb < _WG["every"] and _WG["bytes"] + b_blk * scale <= _WG_HOLD_RAGGED_BYTES and len(lst) + n_blk <= K.GROUP_MAX:
+                return not lst
         # (would one more block of the same size still fit the hold limit and the launch?)
-        if nb < _WG["every"] and _WG["bytes"] * (nb + 1) <= _WG_HOLD_BYTES * nb and len(lst) * (nb + 1) <= K.GROUP_MAX * nb:
+        elif nb < _WG["every"] and _WG["bytes"] * (nb + 1) <= _WG_HOLD_BYTES * nb and len(lst) * (nb + 1) <= K.GROUP_MAX * nb:
             return not lst
-    _WG["blocks"] = 0
-    _WG["bytes"] = 0
+    ends = _WG["ends"]
+    _WG.update(blocks=0, bytes=0, ends=[], blk_bytes=0)
     if lst:
         _WG["list"] = []
         probs = [(dy, a, dw, db, acc) for dy, a, dw, db, acc, _ in lst]
         with _side_stream(*[t for pr in probs for t in pr[:4]]):
-            if not K.gemm_grouped_tn(probs):       # (one problem too: fine-tuning with frozen layers leaves only dWeff)
-                for dy, a, dw, db, acc in probs:
-                    K.gemm(dy, a, dw, dy.shape[1], a.shape[1], dy.shape[0], dy.stride(0), a.stride(0), dw.stride(0),
-                           a_kmajor=False, b_kmajor=False, a_rowsum=db, accumulate=acc)
+            if not _WG["ragged"]:
+                _launch_wgrads(probs)
+            elif not K.gemm_grouped_tn_ragged(probs):
+                # declined as a whole (a token count that is no multiple of 32): block by block, as before round 8
+                bounds = [0] + [e for e in ends if 0 < e < len(probs)] + [len(probs)]
+                for lo, hi in zip(bounds[:-1], bounds[1:]):
+                    if hi > lo:
+                        _launch_wgrads(probs[lo:hi])
             for *_, ready in lst:
                 _ready(*ready)
     return True
@@ -556,10 +589,10 @@ def flush_deferred() -> None:
     fold, ln = _DEFER["fold"], _DEFER["ln"]
     _DEFER["fold"], _DEFER["ln"] = [], []
     if ln:
-        by_shape = {}                         # (one launch per shape of the partial sums: it follows the row count)
-        for e in ln:
-            by_shape.setdefault(tuple(e[0].shape), []).append(e)
-        for es in by_shape.values():
+        by_cols = {}                          # (one launch per width: the row counts of a pruned encoder's blocks differ,
+        for e in ln:                          #  and favit_reduce_rows_multi_ragged takes them together)
+            by_cols.setdefault(e[0].shape[-1], []).append(e)
+        for es in by_cols.values():
             K.reduce_rows_multi([e[:3] for e in es])
         for e in ln:
             _ready(*e[3])
@@ -1197,6 +1230,11 @@ def _tape_cut(tp):
     return tp.cut if isinstance(tp, _NativeTape) else tp[11]
 
 
+def _tape_rows(tp):
+    """Token rows (batch x rows per image) the block of this tape ran on."""
+    return tp.plan.M if isinstance(tp, _NativeTape) else tp[0].shape[0]
+
+
 class EncoderOp:
     """A stack of pre-LN blocks on the fp32 residual stream [B, L, D]:
     x += attn(LN1(x)); x += mlp(LN2(x)).
@@ -1422,7 +1460,8 @@ class EncoderOp:
                     g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dt if more else None)
                     g = g.reshape(B * n_in, D)
                     g_lp = g_lp.reshape(B * n_in, D) if g_lp is not None else g
-                if flush_wgrads(force=False) and _STATE["grad_ready"] is not None:
+                nxt = (_tape_rows(tp), _tape_rows(order[bi + 1][1])) if bi + 1 < len(order) else None
+                if flush_wgrads(force=False, next_rows=nxt) and _STATE["grad_ready"] is not None:
                     flush_deferred()
                 if not _SIDE["enabled"]:
                     join_side_stream()

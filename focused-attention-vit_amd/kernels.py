@@ -198,19 +198,40 @@ def gemm_grouped_tn(problems, use_workspace: bool = True) -> bool:
             if not gemm_grouped_tn(problems[i:i + GROUP_MAX], use_workspace):
                 raise RuntimeError("grouped weight-gradient launch declined a chunk after launching another")
         return True
+    return _grouped_launch(problems, use_workspace, False)
+
+
+def gemm_grouped_tn_ragged(problems, use_workspace: bool = True) -> bool:
+    """gemm_grouped_tn for problems whose token counts differ (the blocks of a pruned encoder in one launch): the
+    library plans K-splits per chunk of problems that share a token count, splits the long blocks into slabs of the
+    workspace and lets the short ones write dW themselves.  Every token count must be a multiple of 32 and the list at
+    most GROUP_MAX long; returns False (nothing launched) otherwise, and the caller falls back."""
+    if len(problems) > GROUP_MAX:
+        return False
+    return _grouped_launch(problems, use_workspace, True)
+
+
+def _grouped_launch(problems, use_workspace, ragged):
     n = len(problems)
     if n == 0:
         return True
+    L = _abi.lib()
+    f_query, f_ws, f_plain = ((L.favit_gemm_grouped_tn_ragged_workspace, L.favit_gemm_grouped_tn_ragged_ws,
+                               L.favit_gemm_grouped_tn_ragged) if ragged else
+                              (L.favit_gemm_grouped_tn_workspace, L.favit_gemm_grouped_tn_ws, L.favit_gemm_grouped_tn))
     arr = (GemmDesc * n)()
     T = problems[0][0].shape[0]
     for d, (dy, a, dw, db, acc) in zip(arr, problems):
         require_gpu(dy, a, dw)
-        if dy.dtype != torch.bfloat16 or a.dtype != torch.bfloat16 or dw.dtype != torch.float32 or dy.shape[0] != T:
+        if dy.dtype != torch.bfloat16 or a.dtype != torch.bfloat16 or dw.dtype != torch.float32:
             return False
+        if a.shape[0] != dy.shape[0] or (dy.shape[0] != T and not ragged):
+            return False
+        T_i = dy.shape[0]
         N, Kd = dy.shape[1], a.shape[1]
         d.A, d.B, d.C = dy.data_ptr(), a.data_ptr(), dw.data_ptr()
         d.a_rowsum = db.data_ptr() if db is not None else None
-        d.M, d.N, d.K = N, Kd, T
+        d.M, d.N, d.K = N, Kd, T_i
         d.lda, d.ldb, d.ldc = dy.stride(0), a.stride(0), dw.stride(0)
         d.batch, d.batch_inner = 1, 1
         d.a_kmajor, d.b_kmajor = 0, 0
@@ -220,7 +241,7 @@ def gemm_grouped_tn(problems, use_workspace: bool = True) -> bool:
     if GEMM_TRACE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    need = int(_abi.lib().favit_gemm_grouped_tn_workspace(arr, n)) if use_workspace else 0
+    need = int(f_query(arr, n)) if use_workspace else 0
     if need > 0:
         dev = problems[0][0].device
         ws = _GROUPED_WS.get(dev.index)
@@ -229,9 +250,9 @@ def gemm_grouped_tn(problems, use_workspace: bool = True) -> bool:
                 _GROUPED_WS_RETIRED.append(ws)
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             _GROUPED_WS[dev.index] = ws
-        rc = _abi.lib().favit_gemm_grouped_tn_ws(arr, n, _p(ws), ws.numel(), _st())
+        rc = f_ws(arr, n, _p(ws), ws.numel(), _st())
     else:
-        rc = _abi.lib().favit_gemm_grouped_tn(arr, n, _st())
+        rc = f_plain(arr, n, _st())
     if rc == -2:
         return False
     _abi.check(rc, "favit_gemm_grouped_tn")
@@ -426,7 +447,10 @@ def layernorm_bwd(dy, x, ldx, gamma, mean, rstd, rows, D, *, dres=None, dx=None,
 
 def reduce_rows_multi(entries):
     """entries: [(part [2, rows, cols] fp32 contiguous, out0 [cols], out1 [cols])] -> out0 += colsum(part[0]),
-    out1 += colsum(part[1]) for every entry in ONE launch (at most 32 entries per launch)."""
+    out1 += colsum(part[1]) for every entry in ONE launch (at most 32 entries per launch).  Entries whose row counts
+    differ (one cols) go through reduce_rows_multi_ragged, still one launch."""
+    if entries and any(tuple(e[0].shape) != tuple(entries[0][0].shape) for e in entries):
+        return reduce_rows_multi_ragged(entries)
     for i in range(0, len(entries), 32):
         chunk = entries[i:i + 32]
         n = len(chunk)
@@ -440,6 +464,27 @@ def reduce_rows_multi(entries):
                                                       arr(*[e[1].data_ptr() for e in chunk]),
                                                       arr(*[e[2].data_ptr() for e in chunk]), rows, cols, _st()),
                    "favit_reduce_rows_multi")
+
+
+def reduce_rows_multi_ragged(entries):
+    """reduce_rows_multi for entries [(part [2, rows_e, cols], out0 [cols], out1 [cols])] whose row counts differ: one
+    launch per 32 entries; every entry is summed as a reduce_rows_multi launch of its own would sum it."""
+    if not entries:
+        return
+    cols = entries[0][0].shape[-1]
+    for part, o0, o1 in entries:                        # validate everything before the first launch
+        require_gpu(part, o0, o1)
+        if part.dim() != 3 or part.shape[0] != 2 or part.shape[2] != cols or not part.is_contiguous() or part.dtype != torch.float32:
+            raise ValueError("reduce_rows_multi: every entry must be a contiguous fp32 [2, rows, cols] stack of one cols")
+    for i in range(0, len(entries), 32):
+        chunk = entries[i:i + 32]
+        n = len(chunk)
+        arr = C.c_void_p * n
+        rows = (C.c_int64 * n)(*[e[0].shape[1] for e in chunk])
+        _abi.check(_abi.lib().favit_reduce_rows_multi_ragged(n, arr(*[e[0].data_ptr() for e in chunk]),
+                                                             arr(*[e[1].data_ptr() for e in chunk]),
+                                                             arr(*[e[2].data_ptr() for e in chunk]), rows, cols, _st()),
+                   "favit_reduce_rows_multi_ragged")
 
 
 def reduce_rows(t2d: torch.Tensor) -> torch.Tensor:

@@ -168,8 +168,25 @@ int favit_gemm_grouped_tn(const favit_gemm_t* gs, int32_t count, void* stream);
 int64_t favit_gemm_grouped_tn_workspace(const favit_gemm_t* gs, int32_t count);
 int favit_gemm_grouped_tn_ws(const favit_gemm_t* gs, int32_t count, void* workspace, int64_t workspace_bytes,
                              void* stream);
-/* Diagnostic: K-splits of the calling host thread's last grouped launch (1 = tiles wrote dW directly). */
+/* The grouped launch for problems whose token counts (K) differ -- the blocks of a pruned encoder.  Consecutive
+ * problems of one K with at most 64 tiles together form a chunk; every chunk gets its own number of K-splits.  Chunks
+ * with one split write dW from the tile epilogue, the others go through per-chunk slabs of the workspace
+ * (favit_gemm_grouped_tn_ragged_workspace bytes; 0 when no chunk is split, and then no reduction kernel runs) that a
+ * second kernel adds in split order.  Every K must be a positive multiple of 32.  A workspace smaller than the query's
+ * answer is FAVIT_ERR_INVALID; without a workspace (the first form) split chunks add with fp32 atomics.  A group with
+ * one K gets exactly the plan and the result of favit_gemm_grouped_tn*.  Nothing is launched when a call is refused. */
+int favit_gemm_grouped_tn_ragged(const favit_gemm_t* gs, int32_t count, void* stream);
+int64_t favit_gemm_grouped_tn_ragged_workspace(const favit_gemm_t* gs, int32_t count);
+int favit_gemm_grouped_tn_ragged_ws(const favit_gemm_t* gs, int32_t count, void* workspace, int64_t workspace_bytes,
+                                    void* stream);
+/* Diagnostic: K-splits of the calling host thread's last grouped launch (1 = tiles wrote dW directly); after a ragged
+ * launch the largest split count among its chunks. */
 int favit_gemm_grouped_last_splits(void);
+/* Diagnostic, host only (nothing is launched): the chunks, per-chunk K-splits and per-XCD unit queues a grouped launch
+ * of these problems gets (ragged != 0: the plan of favit_gemm_grouped_tn_ragged).  out (cap values) receives
+ * {nchunks, units, longest queue in tiles, workspace bytes}, per chunk {first problem, tiles, K, splits, tokens per
+ * split}, per queue {n, unit ids}; returns the number of values written or a negative FAVIT_ERR_*. */
+int favit_gemm_grouped_plan(const favit_gemm_t* gs, int32_t count, int32_t ragged, int64_t* out, int32_t cap);
 
 /* ------------------------------------------------------------------------------------
  * FP8 operand preparation (BASELINE.json configs[3] "fp8 MFMA path"; no reference counterpart:
@@ -250,6 +267,10 @@ int favit_reduce_rows(const float* in, int64_t ld, float* out, int64_t rows, int
  * (each called with dgamma = NULL): the arguments are HOST arrays of n device pointers. */
 int favit_reduce_rows_multi(int32_t n, const float* const* in, float* const* out0, float* const* out1, int64_t rows,
                             int32_t cols, void* stream);
+/* The same for entries of different row counts in ONE launch: rows is a HOST array of n row counts, cols is shared.
+ * Every entry keeps the row split (rows >= 512: eight ways) and the summation order it has in a launch of its own. */
+int favit_reduce_rows_multi_ragged(int32_t n, const float* const* in, float* const* out0, float* const* out1,
+                                   const int64_t* rows, int32_t cols, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * MHLA (models/mhla.py).  latent_proj (mhla.py:41,105-106) is one Linear(hd,hd) shared
