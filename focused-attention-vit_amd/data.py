@@ -38,6 +38,26 @@ def _resized_size(h: int, w: int, size: int) -> Tuple[int, int]:
     return int(size * h / w), size
 
 
+# ---- checkpoint form of a numpy RandomState (plain containers and one tensor), shared by every drawing stage ----
+def _rng_state(rng: np.random.RandomState) -> Dict:
+    name, keys, pos, has_gauss, cached = rng.get_state()
+    return {"bit_generator": str(name), "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos),
+            "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+
+
+def _check_rng_state(who: str, state: Dict) -> None:
+    for k in ("bit_generator", "keys", "pos", "has_gauss", "cached_gaussian"):
+        if k not in state:
+            raise ValueError(f"{who} state: entry '{k}' is missing")
+    if state["bit_generator"] != "MT19937" or tuple(state["keys"].shape) != (624,):
+        raise ValueError(f"{who} state: 'keys' is not the 624-word state of an MT19937 generator")
+
+
+def _set_rng_state(rng: np.random.RandomState, state: Dict) -> None:
+    rng.set_state(("MT19937", state["keys"].numpy().astype(np.uint32), int(state["pos"]), int(state["has_gauss"]),
+                   float(state["cached_gaussian"])))
+
+
 class RaggedBatch:
     """A batch of HWC uint8 images of different sizes, packed back to back (an ImageFolder batch).
 
@@ -131,23 +151,16 @@ class DeviceTransform:
 
     # ---- checkpoint state: the generator of the random crops / flips (plain containers and one tensor) ----
     def state_dict(self) -> Dict:
-        name, keys, pos, has_gauss, cached = self.rng.get_state()
-        return {"kind": self.kind, "bit_generator": str(name), "keys": torch.from_numpy(keys.astype(np.int64)),
-                "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+        return {"kind": self.kind, **_rng_state(self.rng)}
 
     def check_state_dict(self, state: Dict) -> None:
-        for k in ("bit_generator", "keys", "pos", "has_gauss", "cached_gaussian"):
-            if k not in state:
-                raise ValueError(f"DeviceTransform state: entry '{k}' is missing")
-        if state["bit_generator"] != "MT19937" or tuple(state["keys"].shape) != (624,):
-            raise ValueError("DeviceTransform state: 'keys' is not the 624-word state of an MT19937 generator")
+        _check_rng_state("DeviceTransform", state)
         if state.get("kind", self.kind) != self.kind:
             raise ValueError(f"DeviceTransform state: 'kind' is {state['kind']!r}, the transform is {self.kind!r}")
 
     def load_state_dict(self, state: Dict) -> None:
         self.check_state_dict(state)
-        self.rng.set_state(("MT19937", state["keys"].numpy().astype(np.uint32), int(state["pos"]),
-                            int(state["has_gauss"]), float(state["cached_gaussian"])))
+        _set_rng_state(self.rng, state)
 
     # ---- per-image parameter rows (see include/favit.h: favit_image_transform) ----
     def params(self, B: int, H, W) -> np.ndarray:
@@ -326,23 +339,16 @@ class BatchMix:
 
     # ---- checkpoint state: the generator of the draws (the form of DeviceTransform's) ----
     def state_dict(self) -> Dict:
-        name, keys, pos, has_gauss, cached = self.rng.get_state()
-        return {"mode": self.mode, "bit_generator": str(name), "keys": torch.from_numpy(keys.astype(np.int64)),
-                "pos": int(pos), "has_gauss": int(has_gauss), "cached_gaussian": float(cached)}
+        return {"mode": self.mode, **_rng_state(self.rng)}
 
     def check_state_dict(self, state: Dict) -> None:
-        for k in ("bit_generator", "keys", "pos", "has_gauss", "cached_gaussian"):
-            if k not in state:
-                raise ValueError(f"BatchMix state: entry '{k}' is missing")
-        if state["bit_generator"] != "MT19937" or tuple(state["keys"].shape) != (624,):
-            raise ValueError("BatchMix state: 'keys' is not the 624-word state of an MT19937 generator")
+        _check_rng_state("BatchMix", state)
         if state.get("mode", self.mode) != self.mode:
             raise ValueError(f"BatchMix state: 'mode' is {state['mode']!r}, the mix is {self.mode!r}")
 
     def load_state_dict(self, state: Dict) -> None:
         self.check_state_dict(state)
-        self.rng.set_state(("MT19937", state["keys"].numpy().astype(np.uint32), int(state["pos"]),
-                            int(state["has_gauss"]), float(state["cached_gaussian"])))
+        _set_rng_state(self.rng, state)
 
     def _draw(self, S: int):
         """One draw: (lam, (y0, y1, x0, x1)); lam = 1 and a zero box mean 'leave the row alone'."""
@@ -409,14 +415,284 @@ class BatchMix:
         return images, MixedLabels(labels, d_lam)
 
 
+class RandAugment:
+    """torchvision's RandAugment(num_ops, magnitude, num_magnitude_bins) on the device (favit_randaugment): per image
+    num_ops ops drawn uniformly from `ops` (default: all of OPS), each at the magnitude bin `magnitude`, applied to
+    the resized bytes of the transform in ONE launch; the augmented bytes are bit-identical to what Pillow gives
+    for the same ops (torchvision's PIL path, NEAREST interpolation, `fill` outside the image).
+
+    Per image, then per slot, the generator owned by the object draws op = randint(len(ops)) and sign = randint(2)
+    (always drawn; only the signed ops -- shears, translations, Rotate and the four enhancements -- use it).
+    Everything Pillow computes in Python doubles (matrices, fixed-point conversion, masks, thresholds, factors) is
+    computed here and travels in the op table (include/favit.h); the device runs what Pillow runs in C."""
+
+    OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+           "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+    SIGNED = frozenset(OPS[1:10])
+    MAX_OPS = 8            # csrc/augment.hip: AUG_MAX_OPS (favit_randaugment_max_ops)
+    # kernel op ids (include/favit.h)
+    K_IDENTITY, K_AFFINE, K_BLEND, K_MASK, K_SOLARIZE, K_AUTOCONTRAST, K_EQUALIZE = range(7)
+    _BLEND_KIND = {"Brightness": 0, "Color": 1, "Contrast": 2, "Sharpness": 3}
+
+    def __init__(self, num_ops: int = 2, magnitude: int = 9, num_magnitude_bins: int = 31,
+                 fill: Sequence[int] = (0, 0, 0), ops: Optional[Sequence[str]] = None, seed: int = 0):
+        if not 0 <= int(num_ops) <= self.MAX_OPS:
+            raise ValueError(f"RandAugment: num_ops must be in 0..{self.MAX_OPS}, got {num_ops}")
+        if int(num_magnitude_bins) < 2 or not 0 <= int(magnitude) < int(num_magnitude_bins):
+            raise ValueError(f"RandAugment: magnitude {magnitude} is not a bin of {num_magnitude_bins} (at least 2) bins")
+        ops = tuple(self.OPS if ops is None else ops)
+        for name in ops:
+            if name not in self.OPS:
+                raise ValueError(f"RandAugment: unknown op {name!r} (one of {', '.join(self.OPS)})")
+        if not ops:
+            raise ValueError("RandAugment: empty op list")
+        fill = tuple(int(v) for v in ((fill,) * 3 if np.ndim(fill) == 0 else fill))
+        if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+            raise ValueError(f"RandAugment: fill must be three bytes, got {fill}")
+        self.num_ops, self.magnitude, self.bins = int(num_ops), int(magnitude), int(num_magnitude_bins)
+        self.fill, self.ops = fill, ops
+        self.rng = np.random.RandomState(seed)
+
+    # ---- checkpoint state: the generator of the draws (the form of DeviceTransform's) ----
+    def state_dict(self) -> Dict:
+        state = _rng_state(self.rng)
+        state.update(num_ops=self.num_ops, ops=list(self.ops))
+        return state
+
+    def check_state_dict(self, state: Dict) -> None:
+        _check_rng_state("RandAugment", state)
+        if state.get("num_ops", self.num_ops) != self.num_ops or tuple(state.get("ops", self.ops)) != self.ops:
+            raise ValueError("RandAugment state: it was saved with another num_ops / op list, so the generator would "
+                             "not continue the same stream of draws")
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.check_state_dict(state)
+        _set_rng_state(self.rng, state)
+
+    # ---- the op table ----
+    def magnitude_value(self, name: str, S: int, sign: int = 0, bin_: Optional[int] = None):
+        """The magnitude torchvision gives op `name` at the object's bin (or `bin_`) for S x S images; None for the
+        ops without one.  Signed ops are negated when sign == 1."""
+        k, bins = self.magnitude if bin_ is None else int(bin_), self.bins
+        if name in ("Identity", "AutoContrast", "Equalize"):
+            return None
+        if name == "Posterize":
+            return int((8 - np.round(np.arange(bins) / ((bins - 1) / 4)))[k])
+        if name == "Solarize":
+            return float(np.linspace(255.0, 0.0, bins)[k])
+        top = {"ShearX": 0.3, "ShearY": 0.3, "TranslateX": 150.0 / 331.0 * S, "TranslateY": 150.0 / 331.0 * S,
+               "Rotate": 30.0}.get(name, 0.9)
+        m = float(np.linspace(0.0, top, bins)[k])
+        return -m if sign else m
+
+    @staticmethod
+    def _affine_row(mt: Sequence[float], fill: Sequence[int]) -> list:
+        """Pillow's affine_fixed set-up: FIX(v) = floor(v * 65536 + 0.5), the half-pixel centre folded into a2, a5."""
+        a0, a1, a2, a3, a4, a5 = (float(v) for v in mt)
+        fix = lambda v: int(math.floor(v * 65536.0 + 0.5))      # noqa: E731
+        return [RandAugment.K_AFFINE, fix(a0), fix(a1), fix(a2 + a0 * 0.5 + a1 * 0.5), fix(a3), fix(a4),
+                fix(a5 + a3 * 0.5 + a4 * 0.5), fill[0] | fill[1] << 8 | fill[2] << 16]
+
+    def row(self, name: str, m, S: int) -> np.ndarray:
+        """The int32 [8] table row of op `name` with magnitude value m on S x S images."""
+        r = [self.K_IDENTITY] + [0] * 7
+        if name == "ShearX":
+            r = self._affine_row((1, m, 0, 0, 1, 0), self.fill)
+        elif name == "ShearY":
+            r = self._affine_row((1, 0, 0, m, 1, 0), self.fill)
+        elif name == "TranslateX":
+            r = self._affine_row((1, 0, -int(m), 0, 1, 0), self.fill)
+        elif name == "TranslateY":
+            r = self._affine_row((1, 0, 0, 0, 1, -int(m)), self.fill)
+        elif name == "Rotate":
+            # PIL.Image.rotate about the image centre, with its round(..., 15)
+            ang = -math.radians(m % 360.0)
+            mt = [round(math.cos(ang), 15), round(math.sin(ang), 15), 0.0,
+                  round(-math.sin(ang), 15), round(math.cos(ang), 15), 0.0]
+            cx = cy = S / 2.0
+            mt[2] = mt[0] * -cx + mt[1] * -cy + mt[2]
+            mt[5] = mt[3] * -cx + mt[4] * -cy + mt[5]
+            mt[2] += cx
+            mt[5] += cy
+            r = self._affine_row(mt, self.fill)
+        elif name in self._BLEND_KIND:
+            f = np.float32(1 + m)                               # ImageEnhance passes the factor to C as a float
+            r = [self.K_BLEND, self._BLEND_KIND[name], int(f.view(np.int32))] + [0] * 5
+        elif name == "Posterize":
+            r = [self.K_MASK, ~(2 ** (8 - int(m)) - 1) & 0xFF] + [0] * 6
+        elif name == "Solarize":
+            r = [self.K_SOLARIZE, int(math.ceil(m))] + [0] * 6  # integer v < m  <=>  v < ceil(m)
+        elif name == "AutoContrast":
+            r = [self.K_AUTOCONTRAST] + [0] * 7
+        elif name == "Equalize":
+            r = [self.K_EQUALIZE] + [0] * 7
+        elif name != "Identity":
+            raise ValueError(f"RandAugment: unknown op {name!r}")
+        return np.array(r, dtype=np.int64).astype(np.int32)
+
+    def draw(self, B: int) -> np.ndarray:
+        """The draws of one batch: int [B, num_ops, 2] = (index into self.ops, sign)."""
+        d = np.zeros((B, self.num_ops, 2), dtype=np.int64)
+        for b in range(B):
+            for s in range(self.num_ops):
+                d[b, s, 0] = self.rng.randint(len(self.ops))
+                d[b, s, 1] = self.rng.randint(2)
+        return d
+
+    def table(self, draws: np.ndarray, S: int) -> np.ndarray:
+        """int32 [B, num_ops, 8] op table of explicit draws."""
+        B, n = draws.shape[0], draws.shape[1]
+        cache: Dict = {}
+        t = np.zeros((B, n, 8), dtype=np.int32)
+        for b in range(B):
+            for s in range(n):
+                key = (int(draws[b, s, 0]), int(draws[b, s, 1]))
+                if key not in cache:
+                    name = self.ops[key[0]]
+                    cache[key] = self.row(name, self.magnitude_value(name, S, key[1] if name in self.SIGNED else 0), S)
+                t[b, s] = cache[key]
+        return t
+
+    def params(self, B: int, S: int) -> np.ndarray:
+        """A fresh draw for B images of S x S pixels -> the int32 [B, num_ops, 8] op table."""
+        B, S = int(B), int(S)
+        if B < 1 or S < 1:
+            raise ValueError(f"RandAugment.params: B and S must be positive, got {B}, {S}")
+        t = self.table(self.draw(B), S)
+        self.check_params(t, B)
+        return t
+
+    @classmethod
+    def check_params(cls, t: np.ndarray, B: int) -> None:
+        """Refuses a malformed table on the host, before the upload (the kernel would run an unknown op as identity
+        and a non-finite factor as garbage, silently)."""
+        t = np.asarray(t)
+        if t.ndim != 3 or t.shape[0] != B or t.shape[2] != 8 or t.dtype != np.int32:
+            raise ValueError(f"RandAugment: the op table must be int32 [{B}, num_ops, 8]")
+        if t.shape[1] > cls.MAX_OPS:
+            raise ValueError(f"RandAugment: {t.shape[1]} ops per image exceed the kernel's {cls.MAX_OPS}")
+        op = t[:, :, 0]
+        if ((op < 0) | (op > cls.K_EQUALIZE)).any():
+            raise ValueError(f"RandAugment: unknown op id {int(op[(op < 0) | (op > cls.K_EQUALIZE)][0])} in the op table")
+        bl = op == cls.K_BLEND
+        if bl.any():
+            if ((t[:, :, 1][bl] < 0) | (t[:, :, 1][bl] > 3)).any():
+                raise ValueError("RandAugment: a blend row names an unknown degenerate image")
+            if not np.isfinite(np.ascontiguousarray(t[:, :, 2][bl]).view(np.float32)).all():
+                raise ValueError("RandAugment: a blend row carries a non-finite factor")
+        lv = (op == cls.K_MASK) | (op == cls.K_SOLARIZE)
+        if lv.any() and ((t[:, :, 1][lv] < 0) | (t[:, :, 1][lv] > 256)).any():
+            raise ValueError("RandAugment: a Posterize mask / Solarize threshold lies outside 0..256")
+
+    def __call__(self, u8: torch.Tensor, mean, std, params: Optional[np.ndarray] = None, erase_box=None,
+                 erase_value=0.0, erase_seed: int = 0, want_bytes: bool = False):
+        """u8: uint8 [B,S,S,3] on the GPU (the transform's resized bytes) -> fp32 [B,3,S,S], normalized with the
+        transform's mean / std; erase_box (int32 [B,4] on the device) is filled in the same write."""
+        K.require_gpu(u8)
+        if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[1] != u8.shape[2] or u8.shape[3] != 3:
+            raise TypeError("RandAugment expects the uint8 [B, S, S, 3] bytes of a DeviceTransform (RGB images)")
+        B, S = u8.shape[0], u8.shape[1]
+        if params is None:
+            params = self.params(B, S)
+        else:
+            params = np.ascontiguousarray(params)
+            self.check_params(params, B)
+        if params.shape[1] == 0:                                # no ops: one identity slot keeps the table non-empty
+            params = np.zeros((B, 1, 8), dtype=np.int32)
+        ops = torch.from_numpy(params).to(u8.device, non_blocking=True)
+        return K.randaugment(u8.contiguous(), ops, mean, std, erase_box, erase_value, erase_seed, want_bytes)
+
+
+class RandomErasing:
+    """torchvision's RandomErasing(p, scale, ratio, value) on the device: per image, with probability p, up to 10
+    attempts at a box of area * uniform(scale) pixels and log-uniform aspect ratio (h = round(sqrt(a r)), w =
+    round(sqrt(a / r)), accepted when h < H and w < W, origin by randint); an image without an accepted box is left
+    alone.  value: a number, one per channel, or "normal" (one standard-normal value per element from the library's
+    counter-based generator under a per-batch seed the object draws).  Applied after Normalize: by favit_randaugment's
+    final write when a RandAugment runs, else by favit_random_erase in place."""
+
+    def __init__(self, p: float = 0.25, scale: Sequence[float] = (0.02, 0.33), ratio: Sequence[float] = (0.3, 3.3),
+                 value=0, seed: int = 0):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"RandomErasing: p must be in [0, 1], got {p}")
+        if len(scale) != 2 or len(ratio) != 2 or not 0.0 <= scale[0] <= scale[1] <= 1.0 or not 0.0 < ratio[0] <= ratio[1]:
+            raise ValueError(f"RandomErasing: bad scale {scale} / ratio {ratio}")
+        K._erase_fill(value, 3)                                 # refuses a malformed value now
+        self.p, self.scale, self.ratio = float(p), (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        self.value = value if isinstance(value, str) or np.ndim(value) == 0 else tuple(float(v) for v in value)
+        self.rng = np.random.RandomState(seed)
+
+    def state_dict(self) -> Dict:
+        return _rng_state(self.rng)
+
+    def check_state_dict(self, state: Dict) -> None:
+        _check_rng_state("RandomErasing", state)
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.check_state_dict(state)
+        _set_rng_state(self.rng, state)
+
+    def params(self, B: int, H: int, W: int) -> Tuple[np.ndarray, int]:
+        """(box int32 [B,4] = y0, y1, x0, x1 with an empty box meaning no erase, seed of the normal fill)."""
+        B, H, W = int(B), int(H), int(W)
+        if B < 1 or H < 1 or W < 1:
+            raise ValueError(f"RandomErasing.params: B, H and W must be positive, got {B}, {H}, {W}")
+        rng, area = self.rng, H * W
+        lr = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        box = np.zeros((B, 4), dtype=np.int32)
+        for b in range(B):
+            if not rng.rand() < self.p:
+                continue
+            for _ in range(10):
+                a = area * rng.uniform(self.scale[0], self.scale[1])
+                r = math.exp(rng.uniform(lr[0], lr[1]))
+                h, w = int(round(math.sqrt(a * r))), int(round(math.sqrt(a / r)))
+                if not (h < H and w < W):
+                    continue
+                i, j = int(rng.randint(0, H - h + 1)), int(rng.randint(0, W - w + 1))
+                box[b] = (i, i + h, j, j + w)
+                break
+        seed = int(rng.randint(0, 2 ** 31 - 1)) << 31 | int(rng.randint(0, 2 ** 31 - 1))
+        self.check_params(box, B, H, W)
+        return box, seed
+
+    @staticmethod
+    def check_params(box: np.ndarray, B: int, H: int, W: int) -> None:
+        if box.shape != (B, 4) or box.dtype != np.int32:
+            raise ValueError(f"RandomErasing: the box table must be int32 [{B}, 4]")
+        if ((box[:, 0] < 0) | (box[:, 1] > H) | (box[:, 2] < 0) | (box[:, 3] > W)).any():
+            raise ValueError("RandomErasing: a box reaches outside the image")
+
+    def __call__(self, images: torch.Tensor, params=None) -> torch.Tensor:
+        """images: fp32 [B,C,H,W] on the GPU, erased IN PLACE (the stand-alone form)."""
+        K.require_gpu(images)
+        if images.dim() != 4:
+            raise TypeError("RandomErasing expects a [B, C, H, W] batch")
+        B, _, H, W = images.shape
+        box, seed = self.params(B, H, W) if params is None else params
+        box = np.ascontiguousarray(box, dtype=np.int32)
+        self.check_params(box, B, H, W)
+        d_box = torch.from_numpy(box).to(images.device, non_blocking=True)
+        return K.random_erase(images, d_box, self.value, seed)
+
+
 class DeviceLoader:
     """Iterates (images fp32 [B,C,S,S], labels int64 [B]) on the GPU from an iterable of HOST batches
     (uint8 [B,H,W,C] array / tensor, or a RaggedBatch of mixed-size images; integer labels).  Batch k+1 is copied (pinned staging buffers, a dedicated
     copy stream) and transformed while the consumer computes on batch k: no host-side blocking .to(device)."""
 
+    mix = augment = erase = None          # the optional stages (class defaults: off)
+
     def __init__(self, host_batches: Iterable, transform: DeviceTransform, device: Optional[torch.device] = None,
-                 segmenter=None, mix: Optional[BatchMix] = None):
-        """mix (optional): a BatchMix, applied to every batch directly after the transform (with a segmenter: before
+                 segmenter=None, mix: Optional[BatchMix] = None, augment: Optional[RandAugment] = None,
+                 erase: Optional[RandomErasing] = None):
+        """augment (optional): a RandAugment, applied to the resized bytes of the transform before ToTensor / Normalize;
+        erase (optional): a RandomErasing, applied after Normalize (inside the augment's launch when there is one).
+        The order is transform -> RandAugment -> Normalize -> erase -> mix -> segmenter, on both staging paths and for
+        uniform and ragged batches; the state carries their generators under "augment" / "erase".  Without them the
+        loader issues exactly the launches it issues without these options.
+
+        mix (optional): a BatchMix, applied to every batch directly after the transform (with a segmenter: before
         the segmentation, which therefore sees the image the model sees).  The loader then yields
         (images, MixedLabels(labels, lam)) and its state carries the mix's generator under "mix".
 
@@ -434,6 +710,7 @@ class DeviceLoader:
         self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.segmenter, self.mix = segmenter, mix
+        self.augment, self.erase = augment, erase
         # the segmentation stream is confined to SEGMENTER_CUS compute units (streams.py): its grids would otherwise
         # fill every CU and the consumer's short launches would queue behind them
         self.prep_stream = streams.cu_masked_stream(SEGMENTER_CUS, self.dev) if segmenter is not None else None
@@ -448,29 +725,37 @@ class DeviceLoader:
     def state_dict(self) -> Dict:
         state = {"transform": self.tf.state_dict(),
                  "batches": self.src.state_dict() if hasattr(self.src, "state_dict") else None}
-        if self.mix is not None:
-            state["mix"] = self.mix.state_dict()
+        for key, part in self._optional_parts():
+            if part is not None:
+                state[key] = part.state_dict()
         return state
+
+    def _optional_parts(self):
+        return (("mix", self.mix), ("augment", self.augment), ("erase", self.erase))
 
     def check_state_dict(self, state: Dict) -> None:
         for k in ("transform", "batches"):
             if k not in state:
                 raise ValueError(f"DeviceLoader state: entry '{k}' is missing")
-        if ("mix" in state) != (self.mix is not None):
-            raise ValueError("DeviceLoader state: it was saved " + ("with" if "mix" in state else "without") +
-                             " a batch mix and this loader is built " + ("without" if "mix" in state else "with") +
-                             " one")
+        names = {"mix": "a batch mix", "augment": "a RandAugment", "erase": "a RandomErasing"}
+        for key, part in self._optional_parts():
+            if (key in state) != (part is not None):
+                raise ValueError("DeviceLoader state: it was saved " + ("with " if key in state else "without ") +
+                                 names[key] + " and this loader is built " + ("without" if key in state else "with") +
+                                 " one")
         self.tf.check_state_dict(state["transform"])
-        if self.mix is not None:
-            self.mix.check_state_dict(state["mix"])
+        for key, part in self._optional_parts():
+            if part is not None:
+                part.check_state_dict(state[key])
         if state["batches"] is not None and hasattr(self.src, "check_state_dict"):
             self.src.check_state_dict(state["batches"])
 
     def load_state_dict(self, state: Dict) -> None:
         self.check_state_dict(state)
         self.tf.load_state_dict(state["transform"])
-        if self.mix is not None:
-            self.mix.load_state_dict(state["mix"])
+        for key, part in self._optional_parts():
+            if part is not None:
+                part.load_state_dict(state[key])
         if state["batches"] is not None and hasattr(self.src, "load_state_dict"):
             self.src.load_state_dict(state["batches"])
 
@@ -488,6 +773,24 @@ class DeviceLoader:
         buf[0][:n].copy_(rb.bytes)
         buf[1][:B].copy_(labels)
         return RaggedBatch(buf[0][:n], rb.offsets, rb.heights, rb.widths, rb.channels), buf[1][:B]
+
+    def _prepare(self, d_img, d_lab):
+        """transform -> RandAugment -> Normalize -> erase -> mix of one device batch, on the current stream."""
+        if self.augment is not None:
+            _, u8 = self.tf(d_img, want_bytes=True)
+            box, value, seed = None, 0.0, 0
+            if self.erase is not None:
+                S = u8.shape[1]
+                hbox, seed = self.erase.params(u8.shape[0], S, S)
+                box, value = torch.from_numpy(hbox).to(u8.device, non_blocking=True), self.erase.value
+            x = self.augment(u8, self.tf.mean, self.tf.std, erase_box=box, erase_value=value, erase_seed=seed)
+        else:
+            x = self.tf(d_img)
+            if self.erase is not None:
+                x = self.erase(x)
+        if self.mix is not None:
+            return self.mix(x, d_lab)
+        return x, d_lab
 
     def _stage(self, slot: int, imgs, labels):
         ragged = isinstance(imgs, RaggedBatch)
@@ -525,9 +828,7 @@ class DeviceLoader:
             # transform + SLIC of this (next) batch now, on a stream of their own, under the consumer's current step
             with torch.cuda.stream(self.prep_stream):
                 self.prep_stream.wait_event(ev)
-                x = self.tf(d_img)
-                if self.mix is not None:
-                    x, d_lab = self.mix(x, d_lab)
+                x, d_lab = self._prepare(d_img, d_lab)
                 maps = self.segmenter.segment_device(x)
                 derived = self.segmenter.derive_for(maps)        # patch mapping + centroids: functions of the maps alone
                 d_img.record_stream(self.prep_stream)
@@ -571,6 +872,4 @@ class DeviceLoader:
                 self.segmenter.set_label_maps(maps, derived)
             return x, d_lab
         d_img.record_stream(cs)
-        if self.mix is not None:
-            return self.mix(self.tf(d_img), d_lab)
-        return self.tf(d_img), d_lab
+        return self._prepare(d_img, d_lab)

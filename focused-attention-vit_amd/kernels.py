@@ -8,8 +8,10 @@ is never imported from the product).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _abi
@@ -933,6 +935,64 @@ def batch_mix(x, lam, box):
     if box.dtype != torch.int32 or tuple(box.shape) != (B, 4) or not box.is_contiguous():
         raise TypeError("batch_mix: box must be a contiguous int32 [B, 4] tensor of (y0, y1, x0, x1)")
     _abi.check(_abi.lib().favit_batch_mix(_p(x), _p(lam), _p(box), B, Cn, H, W, _st()), "favit_batch_mix")
+    return x
+
+
+def _erase_fill(value, channels):
+    """(host float array, normal flag) of an erase fill: a number, a per-channel sequence or "normal"."""
+    n = max(int(channels), 3)
+    if isinstance(value, str):
+        if value != "normal":
+            raise ValueError(f"erase value {value!r}: a number, a per-channel sequence or 'normal'")
+        return (C.c_float * n)(), 1
+    v = [float(value)] * n if np.ndim(value) == 0 else [float(t) for t in value]
+    if len(v) < channels or not all(math.isfinite(t) for t in v):
+        raise ValueError(f"erase value {value!r}: one finite number, or one per channel ({channels})")
+    v = (v + [v[-1]] * n)[:n]
+    return (C.c_float * n)(*v), 0
+
+
+def randaugment(src_u8, ops, mean, std, erase_box=None, erase_value=0.0, erase_seed=0, want_bytes=False):
+    """favit_randaugment: src_u8 uint8 [B,S,S,3] (the resized bytes of the image transform) through the op rows
+    ops (int32 [B, n_ops, 8] on the device, include/favit.h; data.RandAugment builds them) in one launch -> fp32
+    [B,3,S,S] normalized with mean / std (ctypes float[3]), the erase boxes (int32 [B,4] on the device, or None)
+    filled with erase_value (a number, a per-channel sequence or "normal" under erase_seed) in the same write.
+    Returns out, or (out, augmented bytes [B,S,S,3]) with want_bytes."""
+    require_gpu(src_u8, ops)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[1] != src_u8.shape[2] or not src_u8.is_contiguous():
+        raise TypeError("randaugment: src_u8 must be a contiguous uint8 [B, S, S, C] tensor")
+    B, S, _, Cn = src_u8.shape
+    if ops.dtype != torch.int32 or ops.dim() != 3 or ops.shape[0] != B or ops.shape[2] != 8 or not ops.is_contiguous():
+        raise TypeError(f"randaugment: ops must be a contiguous int32 [{B}, n_ops, 8] tensor")
+    fill, normal = (None, 0)
+    if erase_box is not None:
+        require_gpu(erase_box)
+        if erase_box.dtype != torch.int32 or tuple(erase_box.shape) != (B, 4) or not erase_box.is_contiguous():
+            raise TypeError(f"randaugment: erase_box must be a contiguous int32 [{B}, 4] tensor of (y0, y1, x0, x1)")
+        fill, normal = _erase_fill(erase_value, Cn)
+    dev = src_u8.device
+    scratch = torch.empty((2, B, S, S, Cn), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, Cn, S, S), dtype=torch.float32, device=dev)
+    u8 = torch.empty((B, S, S, Cn), dtype=torch.uint8, device=dev) if want_bytes else None
+    _abi.check(_abi.lib().favit_randaugment(_p(src_u8), _p(scratch), _p(out), _p(u8), _p(ops), int(ops.shape[1]),
+                                            _p(erase_box), fill, normal, int(erase_seed) & 0xFFFFFFFFFFFFFFFF, B, S, Cn,
+                                            mean, std, _st()), "favit_randaugment")
+    return (out, u8) if want_bytes else out
+
+
+def random_erase(x, box, value=0.0, seed=0):
+    """favit_random_erase, in place on x fp32 [B,C,H,W]: the box (y0, y1, x0, x1) of every row (int32 [B,4] on the
+    device; empty = leave the row alone) is filled with `value` (a number, a per-channel sequence, or "normal": one
+    standard-normal value per element under `seed`).  Only the 16-byte groups a box meets are touched.  Returns x."""
+    require_gpu(x, box)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("random_erase: x must be a contiguous fp32 [B, C, H, W] tensor")
+    B, Cn, H, W = x.shape
+    if box.dtype != torch.int32 or tuple(box.shape) != (B, 4) or not box.is_contiguous():
+        raise TypeError(f"random_erase: box must be a contiguous int32 [{B}, 4] tensor of (y0, y1, x0, x1)")
+    fill, normal = _erase_fill(value, Cn)
+    _abi.check(_abi.lib().favit_random_erase(_p(x), _p(box), fill, normal, int(seed) & 0xFFFFFFFFFFFFFFFF, B, Cn, H, W,
+                                             _st()), "favit_random_erase")
     return x
 
 

@@ -628,6 +628,43 @@ int favit_cross_entropy_mix(const float* logits, const int64_t* labels, const fl
                             float* dlogits, int32_t B, int32_t C, float grad_scale, float label_smoothing,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Device RandAugment and Random Erasing (additive in ABI 8).  torchvision's RandAugment(num_ops, magnitude, bins) ops
+ * on RGB PIL images, in the arithmetic Pillow runs in C: the augmented bytes are bit-identical to Pillow's.
+ * ---------------------------------------------------------------------------------- */
+/* src_u8 [B,S,S,C] uint8 (the out_u8 of favit_image_transform*), C == 3, S <= 2048 -> out fp32 [B,C,S,S] =
+ * Normalize(ToTensor(augmented bytes)) with the expression of favit_image_transform, and out_u8 (optional) the
+ * augmented bytes [B,S,S,C].  All ops of an image run inside ONE launch (one workgroup per image).
+ *   scratch: uint8 [2,B,S,S,C] workspace (2 * B * S * S * C bytes), never NULL
+ *   ops: int32 [B, n_ops, 8] DEVICE rows (op, p0 .. p6), 0 <= n_ops <= favit_randaugment_max_ops():
+ *     0 identity
+ *     1 affine, NEAREST: p0..p5 = a0, a1, a2', a3, a4, a5' in 16.16 fixed point, FIX(v) = floor(v * 65536 + 0.5),
+ *       a2' = FIX(a2 + a0/2 + a1/2), a5' = FIX(a5 + a3/2 + a4/2); output (x, y) takes source pixel
+ *       ((a2' + a1 y + a0 x) >> 16, (a5' + a4 y + a3 x) >> 16), or the fill p6 = r | g << 8 | b << 16 outside the image
+ *     2 blend deg + f * (src - deg) in fp32 (unfused), truncated (clipped first unless 0 <= f <= 1): p0 = degenerate
+ *       image (0 black: Brightness; 1 luma L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16: Color; 2 the constant
+ *       int(mean(L) + 0.5): Contrast; 3 the 3x3 SMOOTH filter with its border copied: Sharpness), p1 = bits of f
+ *     3 v & p0 (Posterize)      4 v < p0 ? v : 255 - v (Solarize)
+ *     5 ImageOps.autocontrast   6 ImageOps.equalize      (per channel, from the histogram of the current image)
+ *     any other op id is treated as identity; no table content can cause an out-of-range access
+ *   erase_box (optional): int32 [B,4] DEVICE rows (y0, y1, x0, x1), half open; inside a non-empty box out takes the
+ *     erase fill instead (out_u8 never does): erase_value, a HOST array of 3 floats, per channel -- or, with
+ *     erase_normal != 0, one standard-normal value per element: Box-Muller sqrt(-2 log u1) cos(2 pi u2) on the
+ *     draws 2 idx and 2 idx + 1 of the library's counter-based generator under erase_seed, idx = ((b*C + c)*S + y)*S + x
+ *     (a function of the seed and the element alone).
+ * An all-identity table without erase_box gives the bits of favit_image_transform's out. */
+int favit_randaugment_max_ops(void);
+int favit_randaugment(const uint8_t* src_u8, uint8_t* scratch, float* out, uint8_t* out_u8, const int32_t* ops,
+                      int32_t n_ops, const int32_t* erase_box, const float* erase_value, int32_t erase_normal,
+                      uint64_t erase_seed, int32_t B, int32_t S, int32_t C, const float* mean, const float* std,
+                      void* stream);
+/* The erase alone, in place on x fp32 [B,C,H,W]: box, value (HOST array of max(C, 3) floats; channels past the third
+ * take the third), normal and seed as above with idx = ((b*C + c)*H + y)*W + x.  A box is clipped to the image; only
+ * the 16-byte groups it meets are touched (single elements when W % 4 != 0 or x is not 16-byte aligned), every other
+ * bit of x is left alone.  C * H * W must be below 2^31 and B below 65536 (else FAVIT_ERR_UNSUPPORTED). */
+int favit_random_erase(float* x, const int32_t* box, const float* value, int32_t normal, uint64_t seed, int32_t B,
+                       int32_t C, int32_t H, int32_t W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

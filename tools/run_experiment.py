@@ -169,6 +169,13 @@ def parse_args(argv=None):
                     help="with both alphas > 0: probability that a draw is CutMix rather than Mixup")
     ap.add_argument("--mix_mode", default="batch", choices=["batch", "elem"],
                     help="one draw per batch, or one per image")
+    ap.add_argument("--ra_num_ops", type=int, default=0,
+                    help="RandAugment ops per training image, on the device (default 0: off; the usual recipe is 2)")
+    ap.add_argument("--ra_magnitude", type=int, default=9, help="--ra_num_ops: magnitude bin of 31")
+    ap.add_argument("--erase_prob", type=float, default=0.0,
+                    help="Random Erasing probability per training image (default 0: off; the usual recipe is 0.25)")
+    ap.add_argument("--erase_value", default="zero", choices=["zero", "normal"],
+                    help="--erase_prob: fill the box with 0 or with one standard-normal value per element")
     ap.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine"],
                     help="cosine: linear warm-up over --warmup_epochs, then half a cosine to zero over the remaining epochs")
     ap.add_argument("--warmup_epochs", type=float, default=0.0, help="--lr_schedule cosine: length of the linear warm-up")
@@ -255,7 +262,12 @@ def main(argv=None):
     mix = None
     if a.mixup_alpha > 0 or a.cutmix_alpha > 0:           # training batches only; seeded like the transforms
         mix = pkg.data.BatchMix(a.mixup_alpha, a.cutmix_alpha, a.mix_prob, a.mix_switch_prob, a.mix_mode, seed=a.seed)
-    train_loader = pkg.data.DeviceLoader(train_src, tfs["train"], segmenter=seg, mix=mix)
+    augment = erase = None                                # training batches only, seeded like the transforms
+    if a.ra_num_ops > 0:
+        augment = pkg.data.RandAugment(a.ra_num_ops, a.ra_magnitude, seed=a.seed)
+    if a.erase_prob > 0:
+        erase = pkg.data.RandomErasing(p=a.erase_prob, value="normal" if a.erase_value == "normal" else 0, seed=a.seed)
+    train_loader = pkg.data.DeviceLoader(train_src, tfs["train"], segmenter=seg, mix=mix, augment=augment, erase=erase)
     test_loader = pkg.data.DeviceLoader(test_src, tfs["test"], segmenter=seg)
     work = train_loader.compute_stream if seg is not None else torch.cuda.current_stream()
     work.wait_stream(torch.cuda.current_stream())
