@@ -61,6 +61,11 @@ class BlockDesc(C.Structure):
     ]
 
 
+class BlockMlp(C.Structure):
+    """Mirror of favit_mhla_block_mlp_t (include/favit.h)."""
+    _fields_ = [("x1c", vp), ("n_mlp", i32), ("reserved", i32)]
+
+
 BLOCK_TAPE_SLOTS = ("xn1", "mu1", "rs1", "qkv", "o", "lse", "x1", "xn2", "mu2", "rs2", "h", "pre", "x2")
 BLOCK_BWD_SLOTS = ("dpre", "dxn2", "g1_f32", "g1_lp", "do", "dqkv", "dxn1", "g_out_f32", "g_out_lp", "part1", "part2")
 
@@ -117,6 +122,12 @@ _SIGS = {
     "favit_mhla_block_bwd_layout": ([C.POINTER(BlockDesc), i32, C.POINTER(i64)], C.c_int64),
     "favit_mhla_block_fwd": ([C.POINTER(BlockDesc), vp], C.c_int),
     "favit_mhla_block_bwd": ([C.POINTER(BlockDesc), vp, vp, vp, i64, i32, vp], C.c_int),
+    "favit_mhla_block_tape_layout2": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), C.POINTER(i64)], C.c_int64),
+    "favit_mhla_block_bwd_layout2": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), i32, C.POINTER(i64)], C.c_int64),
+    "favit_mhla_block_attn_fwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp], C.c_int),
+    "favit_mhla_block_mlp_fwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp], C.c_int),
+    "favit_mhla_block_mlp_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
+    "favit_mhla_block_attn_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
     "favit_dropout": ([vp, vp, C.c_int, i64, f32, u64, vp], C.c_int),
     "favit_sppp_map_patches": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_sppp_pool_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),

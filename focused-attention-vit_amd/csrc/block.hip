@@ -38,27 +38,35 @@ int64_t layout(const int64_t* sizes, int n, int64_t* offsets) {
   return off;
 }
 
-void tape_sizes(const favit_mhla_block_t* d, int64_t* s) {
-  const int64_t M = (int64_t)d->B * d->n, D = d->D, Hd = d->hidden;
+// n_mlp: token rows per image of the MLP half (LN2, fc1, fc2 and their backward); n_mlp == d->n is the whole block
+// on one row count (DESIGN.md section 12 has the narrowed block)
+int check_rows(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r) {
+  if (!r) return FAVIT_ERR_INVALID;
+  if (r->n_mlp <= 0 || r->n_mlp > d->n) return FAVIT_ERR_INVALID;
+  return FAVIT_OK;
+}
+
+void tape_sizes(const favit_mhla_block_t* d, int32_t n_mlp, int64_t* s) {
+  const int64_t M = (int64_t)d->B * d->n, Mm = (int64_t)d->B * n_mlp, D = d->D, Hd = d->hidden;
   s[T_XN1] = M * D * 2; s[T_MU1] = M * 4; s[T_RS1] = M * 4;
   s[T_QKV] = M * 3 * D * 2; s[T_O] = M * D * 2;
   s[T_LSE] = d->training ? (int64_t)d->B * d->H * d->n * 4 : 0;
   s[T_X1] = M * D * 4;
-  s[T_XN2] = M * D * 2; s[T_MU2] = M * 4; s[T_RS2] = M * 4;
-  s[T_H] = M * Hd * 2; s[T_PRE] = M * Hd * 2;
-  s[T_X2] = M * D * 4;
+  s[T_XN2] = Mm * D * 2; s[T_MU2] = Mm * 4; s[T_RS2] = Mm * 4;
+  s[T_H] = Mm * Hd * 2; s[T_PRE] = Mm * Hd * 2;
+  s[T_X2] = Mm * D * 4;
 }
 
 int32_t ln_parts(int64_t rows) { return (int32_t)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048); }
 
-void bwd_sizes(const favit_mhla_block_t* d, int want_lp_out, int64_t* s) {
-  const int64_t M = (int64_t)d->B * d->n, D = d->D, Hd = d->hidden;
-  const int64_t part = 2 * (int64_t)ln_parts(M) * D * 4;
-  s[G_DPRE] = M * Hd * 2; s[G_DXN2] = M * D * 2;
-  s[G_G1_F32] = M * D * 4; s[G_G1_LP] = M * D * 2;
+// narrowed (n_mlp < n): g1 leaves the MLP half in fp32 on n_mlp rows; the row cut writes the expanded pair itself
+void bwd_sizes(const favit_mhla_block_t* d, int32_t n_mlp, int want_lp_out, int64_t* s) {
+  const int64_t M = (int64_t)d->B * d->n, Mm = (int64_t)d->B * n_mlp, D = d->D, Hd = d->hidden;
+  s[G_DPRE] = Mm * Hd * 2; s[G_DXN2] = Mm * D * 2;
+  s[G_G1_F32] = Mm * D * 4; s[G_G1_LP] = n_mlp == d->n ? M * D * 2 : 0;
   s[G_DO] = M * D * 2; s[G_DQKV] = M * 3 * D * 2; s[G_DXN1] = M * D * 2;
   s[G_OUT_F32] = M * D * 4; s[G_OUT_LP] = want_lp_out ? M * D * 2 : 0;
-  s[G_PART1] = part; s[G_PART2] = part;
+  s[G_PART1] = 2 * (int64_t)ln_parts(M) * D * 4; s[G_PART2] = 2 * (int64_t)ln_parts(Mm) * D * 4;
 }
 
 // a bf16-in GEMM without batch, split or dropout: the fields every GEMM of the two chains shares
@@ -84,36 +92,14 @@ int check_params(const favit_mhla_block_t* d) {
   if (((uintptr_t)d->tape % ALIGN) != 0 || ((uintptr_t)d->x % 16) != 0) return FAVIT_ERR_ALIGN;
   return FAVIT_OK;
 }
-}  // namespace
 
-extern "C" int64_t favit_mhla_block_tape_layout(const favit_mhla_block_t* desc, int64_t* offsets_out) {
-  const int rc = check_geometry(desc);
-  if (rc != FAVIT_OK) return rc;
-  int64_t s[TAPE_N];
-  tape_sizes(desc, s);
-  return layout(s, TAPE_N, offsets_out);
-}
-
-extern "C" int64_t favit_mhla_block_bwd_layout(const favit_mhla_block_t* desc, int32_t want_lp_out, int64_t* offsets_out) {
-  const int rc = check_geometry(desc);
-  if (rc != FAVIT_OK) return rc;
-  int64_t s[BWD_N];
-  bwd_sizes(desc, want_lp_out, s);
-  return layout(s, BWD_N, offsets_out);
-}
-
-extern "C" int favit_mhla_block_fwd(const favit_mhla_block_t* d, void* stream) {
-  int rc = check_geometry(d);
-  if (rc != FAVIT_OK) return rc;
-  if ((rc = check_params(d)) != FAVIT_OK) return rc;
-  int64_t s[TAPE_N], o[TAPE_N];
-  tape_sizes(d, s);
-  if (d->tape_bytes < layout(s, TAPE_N, o)) return FAVIT_ERR_INVALID;
-  // ---- nothing has been launched above this line ----
+// ---- the four launch sequences; every argument has been validated by the caller ----
+// LN1, qkv, attention, proj + residual on B * n rows: x1 lands in the tape
+int attn_half_fwd(const favit_mhla_block_t* d, const int64_t* o, void* stream) {
+  int rc;
   char* t = reinterpret_cast<char*>(d->tape);
   const int64_t M = (int64_t)d->B * d->n;
-  const int32_t D = d->D, Hd = d->hidden;
-  float* x1 = reinterpret_cast<float*>(t + o[T_X1]);
+  const int32_t D = d->D;
   if ((rc = favit_layernorm_fwd(d->x, D, d->g1, d->b1, t + o[T_XN1], FAVIT_BF16, reinterpret_cast<float*>(t + o[T_MU1]),
                                 reinterpret_cast<float*>(t + o[T_RS1]), M, D, d->eps, stream)) != FAVIT_OK)
     return rc;
@@ -126,58 +112,60 @@ extern "C" int favit_mhla_block_fwd(const favit_mhla_block_t* d, void* stream) {
                    : favit_mhla_attn_fwd(t + o[T_QKV], t + o[T_O], nullptr, d->B, d->n, d->H, 64, d->W, FAVIT_BF16, 0.f, 0,
                                          stream);
   if (rc != FAVIT_OK) return rc;
-  g = gemm_base(t + o[T_O], d->wproj, x1, M, D, D, D, 1, FAVIT_F32);
+  g = gemm_base(t + o[T_O], d->wproj, t + o[T_X1], M, D, D, D, 1, FAVIT_F32);
   g.bias = d->bproj; g.residual = d->x;
   g.ld_aux_out = D; g.ld_res = D;
-  if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
+  return favit_gemm(&g, stream);
+}
+
+// LN2, fc1, fc2 + residual on Mm rows of x1 (the tape's x1, or the caller's cut copy of it)
+int mlp_half_fwd(const favit_mhla_block_t* d, const float* x1, int64_t Mm, const int64_t* o, void* stream) {
+  int rc;
+  char* t = reinterpret_cast<char*>(d->tape);
+  const int32_t D = d->D, Hd = d->hidden;
   if ((rc = favit_layernorm_fwd(x1, D, d->g2, d->b2, t + o[T_XN2], FAVIT_BF16, reinterpret_cast<float*>(t + o[T_MU2]),
-                                reinterpret_cast<float*>(t + o[T_RS2]), M, D, d->eps, stream)) != FAVIT_OK)
+                                reinterpret_cast<float*>(t + o[T_RS2]), Mm, D, d->eps, stream)) != FAVIT_OK)
     return rc;
-  g = gemm_base(t + o[T_XN2], d->wfc1, t + o[T_H], M, Hd, D, D, 1, FAVIT_BF16);
+  favit_gemm_t g = gemm_base(t + o[T_XN2], d->wfc1, t + o[T_H], Mm, Hd, D, D, 1, FAVIT_BF16);
   g.bias = d->bfc1; g.act = FAVIT_ACT_GELU_SAVEGRAD; g.aux_out = t + o[T_PRE];
   g.ld_aux_out = Hd; g.ld_res = Hd;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  g = gemm_base(t + o[T_H], d->wfc2, t + o[T_X2], M, D, Hd, Hd, 1, FAVIT_F32);
+  g = gemm_base(t + o[T_H], d->wfc2, t + o[T_X2], Mm, D, Hd, Hd, 1, FAVIT_F32);
   g.bias = d->bfc2; g.residual = x1;
   g.ld_aux_out = D; g.ld_res = D;
   return favit_gemm(&g, stream);
 }
 
-extern "C" int favit_mhla_block_bwd(const favit_mhla_block_t* d, const float* g_f32, const void* g_lp, void* bwd_buffers,
-                                    int64_t bwd_bytes, int32_t want_lp_out, void* stream) {
-  int rc = check_geometry(d);
-  if (rc != FAVIT_OK) return rc;
-  if ((rc = check_params(d)) != FAVIT_OK) return rc;
-  if (!d->training || !g_f32 || !g_lp || !bwd_buffers) return FAVIT_ERR_INVALID;
-  if (((uintptr_t)bwd_buffers % ALIGN) != 0 || ((uintptr_t)g_f32 % 16) != 0 || ((uintptr_t)g_lp % 16) != 0)
-    return FAVIT_ERR_ALIGN;
-  int64_t s[TAPE_N], o[TAPE_N], bs[BWD_N], b[BWD_N];
-  tape_sizes(d, s);
-  if (d->tape_bytes < layout(s, TAPE_N, o)) return FAVIT_ERR_INVALID;
-  bwd_sizes(d, want_lp_out, bs);
-  if (bwd_bytes < layout(bs, BWD_N, b)) return FAVIT_ERR_INVALID;
-  // ---- nothing has been launched above this line ----
+// dpre, dxn2, LayerNorm 2 backward on Mm rows; g1_lp == nullptr: a row cut follows and writes the copy
+int mlp_half_bwd(const favit_mhla_block_t* d, const float* x1, int64_t Mm, const float* g_f32, const void* g_lp,
+                 const int64_t* o, char* w, const int64_t* b, void* g1_lp, void* stream) {
+  int rc;
   char* t = reinterpret_cast<char*>(d->tape);
-  char* w = reinterpret_cast<char*>(bwd_buffers);
-  const int64_t M = (int64_t)d->B * d->n;
-  const int32_t D = d->D, Hd = d->hidden, np = ln_parts(M);
-  float* g1 = reinterpret_cast<float*>(w + b[G_G1_F32]);
-  float* part1 = reinterpret_cast<float*>(w + b[G_PART1]);
+  const int32_t D = d->D, Hd = d->hidden, np = ln_parts(Mm);
   float* part2 = reinterpret_cast<float*>(w + b[G_PART2]);
   // dpre = (g . W2) * gelu'(pre): dX = dY.W with the weight [N, K] read mn-major
-  favit_gemm_t g = gemm_base(g_lp, d->wfc2, w + b[G_DPRE], M, Hd, D, Hd, 0, FAVIT_BF16);
+  favit_gemm_t g = gemm_base(g_lp, d->wfc2, w + b[G_DPRE], Mm, Hd, D, Hd, 0, FAVIT_BF16);
   g.act = FAVIT_ACT_MULAUX; g.aux_in = t + o[T_PRE]; g.ld_aux_in = Hd;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  g = gemm_base(w + b[G_DPRE], d->wfc1, w + b[G_DXN2], M, D, Hd, D, 0, FAVIT_BF16);
+  g = gemm_base(w + b[G_DPRE], d->wfc1, w + b[G_DXN2], Mm, D, Hd, D, 0, FAVIT_BF16);
   g.ld_aux_in = D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
   // LayerNorm 2 backward: the partial sums stay in part2 (dgamma = NULL: the caller folds them later)
-  if ((rc = favit_layernorm_bwd(w + b[G_DXN2], FAVIT_BF16, reinterpret_cast<const float*>(t + o[T_X1]), D, d->g2,
-                                reinterpret_cast<const float*>(t + o[T_MU2]), reinterpret_cast<const float*>(t + o[T_RS2]),
-                                g_f32, g1, D, w + b[G_G1_LP], FAVIT_BF16, part2, part2 + (int64_t)np * D, np, nullptr,
-                                nullptr, 1, M, D, 0.f, 0, stream)) != FAVIT_OK)
-    return rc;
-  g = gemm_base(w + b[G_G1_LP], d->wproj, w + b[G_DO], M, D, D, D, 0, FAVIT_BF16);
+  return favit_layernorm_bwd(w + b[G_DXN2], FAVIT_BF16, x1, D, d->g2, reinterpret_cast<const float*>(t + o[T_MU2]),
+                             reinterpret_cast<const float*>(t + o[T_RS2]), g_f32, reinterpret_cast<float*>(w + b[G_G1_F32]),
+                             D, g1_lp, FAVIT_BF16, part2, part2 + (int64_t)np * D, np, nullptr, nullptr, 1, Mm, D, 0.f, 0,
+                             stream);
+}
+
+// do, attention backward, dxn1, LayerNorm 1 backward on B * n rows
+int attn_half_bwd(const favit_mhla_block_t* d, const float* g1, const void* g1_lp, const int64_t* o, char* w,
+                  const int64_t* b, int want_lp_out, void* stream) {
+  int rc;
+  char* t = reinterpret_cast<char*>(d->tape);
+  const int64_t M = (int64_t)d->B * d->n;
+  const int32_t D = d->D, np = ln_parts(M);
+  float* part1 = reinterpret_cast<float*>(w + b[G_PART1]);
+  favit_gemm_t g = gemm_base(g1_lp, d->wproj, w + b[G_DO], M, D, D, D, 0, FAVIT_BF16);
   g.ld_aux_in = D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
   if ((rc = favit_mhla_attn_bwd_lse(t + o[T_QKV], w + b[G_DO], t + o[T_O], reinterpret_cast<const float*>(t + o[T_LSE]),
@@ -191,4 +179,144 @@ extern "C" int favit_mhla_block_bwd(const favit_mhla_block_t* d, const float* g_
                              reinterpret_cast<const float*>(t + o[T_RS1]), g1, reinterpret_cast<float*>(w + b[G_OUT_F32]), D,
                              want_lp_out ? w + b[G_OUT_LP] : nullptr, FAVIT_BF16, part1, part1 + (int64_t)np * D, np, nullptr,
                              nullptr, 1, M, D, 0.f, 0, stream);
+}
+
+// what every chain call checks before its first launch; fills the tape offsets
+int check_call(const favit_mhla_block_t* d, int32_t n_mlp, int64_t* o) {
+  int rc = check_params(d);
+  if (rc != FAVIT_OK) return rc;
+  int64_t s[TAPE_N];
+  tape_sizes(d, n_mlp, s);
+  return d->tape_bytes < layout(s, TAPE_N, o) ? FAVIT_ERR_INVALID : FAVIT_OK;
+}
+
+// the same for a backward call: training, the gradient pair and the arena; fills the arena offsets
+int check_bwd_call(const favit_mhla_block_t* d, int32_t n_mlp, const float* g_f32, const void* g_lp, void* bwd_buffers,
+                   int64_t bwd_bytes, int32_t want_lp_out, int64_t* o, int64_t* b) {
+  int rc = check_params(d);
+  if (rc != FAVIT_OK) return rc;
+  if (!d->training || !g_f32 || !g_lp || !bwd_buffers) return FAVIT_ERR_INVALID;
+  if (((uintptr_t)bwd_buffers % ALIGN) != 0 || ((uintptr_t)g_f32 % 16) != 0 || ((uintptr_t)g_lp % 16) != 0)
+    return FAVIT_ERR_ALIGN;
+  int64_t s[TAPE_N], bs[BWD_N];
+  tape_sizes(d, n_mlp, s);
+  if (d->tape_bytes < layout(s, TAPE_N, o)) return FAVIT_ERR_INVALID;
+  bwd_sizes(d, n_mlp, want_lp_out, bs);
+  if (bwd_bytes < layout(bs, BWD_N, b)) return FAVIT_ERR_INVALID;
+  return FAVIT_OK;
+}
+
+int check_x1c(const favit_mhla_block_mlp_t* r) {
+  if (!r->x1c) return FAVIT_ERR_INVALID;
+  return ((uintptr_t)r->x1c % 16) != 0 ? FAVIT_ERR_ALIGN : FAVIT_OK;
+}
+}  // namespace
+
+extern "C" int64_t favit_mhla_block_tape_layout(const favit_mhla_block_t* desc, int64_t* offsets_out) {
+  const int rc = check_geometry(desc);
+  if (rc != FAVIT_OK) return rc;
+  int64_t s[TAPE_N];
+  tape_sizes(desc, desc->n, s);
+  return layout(s, TAPE_N, offsets_out);
+}
+
+extern "C" int64_t favit_mhla_block_bwd_layout(const favit_mhla_block_t* desc, int32_t want_lp_out, int64_t* offsets_out) {
+  const int rc = check_geometry(desc);
+  if (rc != FAVIT_OK) return rc;
+  int64_t s[BWD_N];
+  bwd_sizes(desc, desc->n, want_lp_out, s);
+  return layout(s, BWD_N, offsets_out);
+}
+
+extern "C" int favit_mhla_block_fwd(const favit_mhla_block_t* d, void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  int64_t o[TAPE_N];
+  if ((rc = check_call(d, d->n, o)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  if ((rc = attn_half_fwd(d, o, stream)) != FAVIT_OK) return rc;
+  return mlp_half_fwd(d, reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[T_X1]), (int64_t)d->B * d->n, o,
+                      stream);
+}
+
+extern "C" int favit_mhla_block_bwd(const favit_mhla_block_t* d, const float* g_f32, const void* g_lp, void* bwd_buffers,
+                                    int64_t bwd_bytes, int32_t want_lp_out, void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  int64_t o[TAPE_N], b[BWD_N];
+  if ((rc = check_bwd_call(d, d->n, g_f32, g_lp, bwd_buffers, bwd_bytes, want_lp_out, o, b)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  char* w = reinterpret_cast<char*>(bwd_buffers);
+  const float* x1 = reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[T_X1]);
+  if ((rc = mlp_half_bwd(d, x1, (int64_t)d->B * d->n, g_f32, g_lp, o, w, b, w + b[G_G1_LP], stream)) != FAVIT_OK) return rc;
+  return attn_half_bwd(d, reinterpret_cast<const float*>(w + b[G_G1_F32]), w + b[G_G1_LP], o, w, b, want_lp_out, stream);
+}
+
+// ---- the block in two halves with a row cut between them ----
+extern "C" int64_t favit_mhla_block_tape_layout2(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows,
+                                                 int64_t* offsets_out) {
+  int rc = check_geometry(desc);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(desc, rows)) != FAVIT_OK) return rc;
+  int64_t s[TAPE_N];
+  tape_sizes(desc, rows->n_mlp, s);
+  return layout(s, TAPE_N, offsets_out);
+}
+
+extern "C" int64_t favit_mhla_block_bwd_layout2(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows,
+                                                int32_t want_lp_out, int64_t* offsets_out) {
+  int rc = check_geometry(desc);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(desc, rows)) != FAVIT_OK) return rc;
+  int64_t s[BWD_N];
+  bwd_sizes(desc, rows->n_mlp, want_lp_out, s);
+  return layout(s, BWD_N, offsets_out);
+}
+
+extern "C" int favit_mhla_block_attn_fwd(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r, void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(d, r)) != FAVIT_OK) return rc;
+  int64_t o[TAPE_N];
+  if ((rc = check_call(d, r->n_mlp, o)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  return attn_half_fwd(d, o, stream);
+}
+
+extern "C" int favit_mhla_block_mlp_fwd(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r, void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(d, r)) != FAVIT_OK) return rc;
+  if ((rc = check_x1c(r)) != FAVIT_OK) return rc;
+  int64_t o[TAPE_N];
+  if ((rc = check_call(d, r->n_mlp, o)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  return mlp_half_fwd(d, r->x1c, (int64_t)d->B * r->n_mlp, o, stream);
+}
+
+extern "C" int favit_mhla_block_mlp_bwd(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r, const float* g_f32,
+                                        const void* g_lp, void* bwd_buffers, int64_t bwd_bytes, int32_t want_lp_out,
+                                        void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(d, r)) != FAVIT_OK) return rc;
+  if ((rc = check_x1c(r)) != FAVIT_OK) return rc;
+  int64_t o[TAPE_N], b[BWD_N];
+  if ((rc = check_bwd_call(d, r->n_mlp, g_f32, g_lp, bwd_buffers, bwd_bytes, want_lp_out, o, b)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  char* w = reinterpret_cast<char*>(bwd_buffers);
+  return mlp_half_bwd(d, r->x1c, (int64_t)d->B * r->n_mlp, g_f32, g_lp, o, w, b,
+                      r->n_mlp == d->n ? w + b[G_G1_LP] : nullptr, stream);
+}
+
+extern "C" int favit_mhla_block_attn_bwd(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r, const float* g1_f32,
+                                         const void* g1_lp, void* bwd_buffers, int64_t bwd_bytes, int32_t want_lp_out,
+                                         void* stream) {
+  int rc = check_geometry(d);
+  if (rc != FAVIT_OK) return rc;
+  if ((rc = check_rows(d, r)) != FAVIT_OK) return rc;
+  int64_t o[TAPE_N], b[BWD_N];
+  if ((rc = check_bwd_call(d, r->n_mlp, g1_f32, g1_lp, bwd_buffers, bwd_bytes, want_lp_out, o, b)) != FAVIT_OK) return rc;
+  // ---- nothing has been launched above this line ----
+  return attn_half_bwd(d, g1_f32, g1_lp, o, reinterpret_cast<char*>(bwd_buffers), b, want_lp_out, stream);
 }

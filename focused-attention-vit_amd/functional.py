@@ -1161,6 +1161,30 @@ def cls_only_cuts(specs: Sequence["BlockSpec"], L: int, mask, training: bool):
     return plan if any(c is not None for c in plan) else None
 
 
+def mlp_narrow_plan(cuts: Sequence[Optional[Tuple[int, int]]], after: Optional[Tuple[int, int]] = None):
+    """Rows of every block's MLP half.  Only attention mixes rows: proj, LayerNorm 2, fc1, fc2
+    and the residual adds are row-wise, and the block after block k reads just its own (head, tail) rows of block k's
+    output, so the cut between the two blocks can sit between block k's attention half and its MLP half.
+    cuts: the cls_plan entries of the blocks of ONE encoder node; after: the rows the stream must have behind the node
+    (the first block of the next graph segment), None where nobody said -- the node's last block then keeps its rows
+    (the last block of the encoder always does: the caller reads its rows).  Entry k is the (head, tail) pair block
+    k's MLP half runs on, or None for "the rows of its attention half".  A block on all rows (cuts[k] is None) that is
+    followed by a narrower one narrows too."""
+    cuts = list(cuts)
+    out: List[Optional[Tuple[int, int]]] = []
+    for k, c in enumerate(cuts):
+        nxt = cuts[k + 1] if k + 1 < len(cuts) else after
+        out.append(tuple(nxt) if nxt is not None and (c is None or sum(nxt) < sum(c)) else None)
+    return out
+
+
+def mlp_narrow_on() -> bool:
+    """A/B switch of the narrowed MLP halves (default on): FAVIT_NO_MLP_NARROW=1, read at each call like
+    FAVIT_NO_NATIVE_BLOCKS, restores a cut in front of every block.  K.GEMM_TRACE holds every block on one row count as
+    well: its readers (tests/test_gpu_native_blocks.py) look every GEMM of a block up under the block's own rows."""
+    return not os.environ.get("FAVIT_NO_MLP_NARROW") and K.GEMM_TRACE is None
+
+
 # Native block chains (DESIGN.md section 10): where a block is MHLA + MLP in bf16 without mask or dropout, the seven
 # launches of its forward and the seven of its input-gradient chain are issued by ONE library call each
 # (favit_mhla_block_fwd / _bwd) instead of one Python wrapper call each, with its allocations and its descriptor.  The
@@ -1195,11 +1219,15 @@ class _NativeTape:
     """What a native block forward left for backward: ONE device allocation (buf, carved by plan.off) plus the
     references the Python tape tuple holds.  Tensor views of the allocation are made only when somebody asks:
     the native backward needs four of them (the weight-gradient operands), the Python backward all (unpack)."""
-    __slots__ = ("plan", "buf", "x", "ln", "pa", "pm", "weff", "wc", "cut", "_bf", "_f32")
+    __slots__ = ("plan", "buf", "x", "ln", "pa", "pm", "weff", "wc", "cut", "mcut", "x1c", "mlp", "arena", "_bf", "_f32")
 
-    def __init__(self, plan, buf, x, ln, pa, pm, weff, wc, cut):
+    def __init__(self, plan, buf, x, ln, pa, pm, weff, wc, cut, mcut=None, x1c=None, mlp=None):
+        """mcut = (n, head, tail): the MLP half ran on head + tail of the block's n rows, on x1c (the cut copy of the
+        tape's x1; held here for backward).  mlp: what the Python chain left of that half, (xn2, mu2, rs2, sm, x2),
+        where the library declined its call; None: the half is in the tape."""
         self.plan, self.buf, self.x, self.ln, self.pa, self.pm, self.weff, self.wc, self.cut = \
             plan, buf, x, ln, pa, pm, weff, wc, cut
+        self.mcut, self.x1c, self.mlp, self.arena = mcut, x1c, mlp, None
         self._bf = self._f32 = None
 
     def bf(self, name, *shape):
@@ -1215,24 +1243,36 @@ class _NativeTape:
     def unpack(self):
         """The tape tuple EncoderOp.fwd's Python path would have built for this block (EncoderOp.bwd reads it)."""
         pl = self.plan
-        M, D, Hd = pl.M, pl.D, pl.hidden
+        M, Mm, D, Hd = pl.M, pl.Mm, pl.D, pl.hidden
         (g1, b1, g2, b2), (wp_c, w1_c, w2_c) = self.ln, self.wc
         lse = self.f32("lse", pl.B, pl.H, pl.n) if pl.off["lse"][1] else None
         sa = (self.bf("xn1", M, D), self.weff, self.bf("qkv", M, 3 * D), self.bf("o", M, D), wp_c, None, pl.B, pl.n,
               0.0, 0, 0.0, 0, self.pa, lse)
-        sm = (self.bf("xn2", M, D), (self.bf("pre", M, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)), self.bf("h", M, Hd),
-              w1_c, w2_c, 0.0, 0, 0, self.pm)
-        return (self.x, self.f32("mu1", M), self.f32("rs1", M), (g1, b1), sa, self.f32("x1", M, D), self.f32("mu2", M),
-                self.f32("rs2", M), (g2, b2), sm, (self.pa, self.pm), self.cut)
+        if self.mlp is not None:
+            _, mu2, rs2, sm, _ = self.mlp
+        else:
+            sm = (self.bf("xn2", Mm, D), (self.bf("pre", Mm, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)),
+                  self.bf("h", Mm, Hd), w1_c, w2_c, 0.0, 0, 0, self.pm)
+            mu2, rs2 = self.f32("mu2", Mm), self.f32("rs2", Mm)
+        x1 = self.x1c if self.mcut is not None else self.f32("x1", M, D)
+        return (self.x, self.f32("mu1", M), self.f32("rs1", M), (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm,
+                (self.pa, self.pm), self.cut, self.mcut)
 
 
 def _tape_cut(tp):
     return tp.cut if isinstance(tp, _NativeTape) else tp[11]
 
 
+def _tape_mcut(tp):
+    return tp.mcut if isinstance(tp, _NativeTape) else tp[12]
+
+
 def _tape_rows(tp):
-    """Token rows (batch x rows per image) the block of this tape ran on."""
-    return tp.plan.M if isinstance(tp, _NativeTape) else tp[0].shape[0]
+    """Token rows (batch x rows per image) the block of this tape holds operands for: those of its attention half plus
+    those of its MLP half (the ratio of two blocks scales the bytes their weight-gradient operands keep alive)."""
+    if isinstance(tp, _NativeTape):
+        return tp.plan.M + tp.plan.Mm
+    return tp[0].shape[0] + tp[5].shape[0]
 
 
 class EncoderOp:
@@ -1241,13 +1281,19 @@ class EncoderOp:
     cuts (CLS-only mode, see cls_plan): per block the (head, tail) rows it runs on, or None for all rows.  The stream
     is cut to a block's rows in front of it (favit_rows_cut_fwd), the block runs on the compact [B, n, D] tensor with
     L = n throughout, and the output keeps the last block's rows; backward expands at the same points
-    (favit_rows_cut_bwd)."""
+    (favit_rows_cut_bwd).
+    mlp_cuts (mlp_narrow_plan): per block the (head, tail) rows its MLP half runs on, or None.  The stream is then cut
+    inside the block, after proj + residual, and the next block finds its rows in place: the cut in front of it moves
+    up into this block."""
 
-    def __init__(self, blocks: List[BlockSpec], mask=None, training=False, cuts=None):
+    def __init__(self, blocks: List[BlockSpec], mask=None, training=False, cuts=None, mlp_cuts=None):
         self.blocks, self.mask, self.training = blocks, mask, training
         self.cuts = list(cuts) if cuts is not None else None
         if self.cuts is not None and (len(self.cuts) != len(blocks) or mask is not None):
             raise ValueError("cuts: one entry per block, and no attention mask")
+        self.mlp_cuts = list(mlp_cuts) if mlp_cuts is not None else None
+        if self.mlp_cuts is not None and (self.cuts is None or len(self.mlp_cuts) != len(blocks)):
+            raise ValueError("mlp_cuts: one entry per block of an encoder with cuts")
 
     def fwd(self, ins, prm):
         (x,) = ins
@@ -1290,11 +1336,17 @@ class EncoderOp:
                 cut = (L, ca, cb)
                 L = ca + cb
                 M = B * L
+            mc = self.mlp_cuts[bi] if self.mlp_cuts is not None else None
+            if mc is not None and sum(mc) >= L:
+                mc = None
             if native and pre[bi] is not None:
-                nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut)
+                nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut, mc)
                 if nt is not None:
                     tapes.append(nt)
-                    x = nt.f32("x2", M, D)
+                    if mc is not None:
+                        L = sum(mc)
+                        M = B * L
+                    x = nt.f32("x2", M, D) if nt.mlp is None else nt.mlp[4]
                     continue
             fuse = fuse_ok and M <= 16384
             if fuse and isinstance(bs.attn, (MHLAChain, DenseChain)):
@@ -1308,21 +1360,36 @@ class EncoderOp:
                     x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training, pre=pre[bi])
                 else:
                     x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training)
-            if fuse and isinstance(bs.mlp, MLPChain):
-                o2 = [None, None, None]
-                x2, sm = bs.mlp.fwd(None, pm, x1, self.training, ln=(x1, g2.detach(), b2.detach(), o2))
-                xn2, mu2, rs2 = o2
-            else:
-                xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
-                x2, sm = bs.mlp.fwd(xn2, pm, x1, self.training)
-            tapes.append((x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa, pm), cut))
+            mcut = None
+            if mc is not None:
+                # the rows the next block reads: everything from here on is row-wise, so the cut comes first
+                x1 = K.rows_cut_fwd(x1, B, L, mc[0], mc[1], D).reshape(B * sum(mc), D)
+                mcut = (L, mc[0], mc[1])
+                L = sum(mc)
+                M = B * L
+            xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
+            tapes.append((x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa, pm), cut, mcut))
             x = x2
         return x.reshape(B, L, D), (tapes, B, L_in, D)
 
-    def _fwd_native(self, bs, p, x, B, L, D, pre, cut):
+    def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, fuse_ok):
+        """LayerNorm 2 and the MLP chain on the M rows of x1 (the Python chains)."""
+        if fuse_ok and M <= 16384 and isinstance(bs.mlp, MLPChain):
+            o2 = [None, None, None]
+            x2, sm = bs.mlp.fwd(None, pm, x1, self.training, ln=(x1, g2.detach(), b2.detach(), o2))
+            xn2, mu2, rs2 = o2
+        else:
+            xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
+            x2, sm = bs.mlp.fwd(xn2, pm, x1, self.training)
+        return xn2, mu2, rs2, sm, x2
+
+    def _fwd_native(self, bs, p, x, B, L, D, pre, cut, mc=None):
         """One block's forward as one library call, or None where this block runs the Python chains: not MHLA + MLP, a
         dropout that is active in this mode, parameters of another dtype or shape than the chain assumes, a geometry
-        the library declines (favit_mhla_block_tape_layout), or a declined call (nothing was launched then)."""
+        the library declines (favit_mhla_block_tape_layout), or a declined call (nothing was launched then).
+        mc = (head, tail): the MLP half runs on those rows -- the attention half as one call, the Python-visible row
+        cut of x1, then the MLP half as a second call on the same descriptor (where the library declines that one,
+        the Python chain runs the half and the tape holds its tensors)."""
         at, ml = bs.attn, bs.mlp
         if not (isinstance(at, MHLAChain) and isinstance(ml, MLPChain)) or len(p) != 14:
             return None
@@ -1344,15 +1411,23 @@ class EncoderOp:
         if plans is None:
             plans = g1._favit_blocks = {}
         key = (B, L, D, at.H, at.W, Hd, bool(self.training))
+        if mc is not None:
+            key += (sum(mc),)
         if key not in plans:
-            plans[key] = K.mhla_block_plan(*key)
+            plans[key] = K.mhla_block_plan(*key[:7], n_mlp=sum(mc)) if mc is not None else K.mhla_block_plan(*key)
         plan = plans[key]
         if plan is None:
             return None
         buf = torch.empty(plan.tape_bytes, dtype=torch.uint8, device=x.device)
         if K.mhla_block_fwd(plan, x, buf, g1, b1, g2, b2, weff, beff, wc[0], bp, wc[1], c1, wc[2], c2) != 0:
             return None
-        return _NativeTape(plan, buf, x, (g1, b1, g2, b2), p[2:8], p[10:], weff, wc, cut)
+        nt = _NativeTape(plan, buf, x, (g1, b1, g2, b2), p[2:8], p[10:], weff, wc, cut)
+        if mc is not None:
+            nt.mcut = (L, mc[0], mc[1])
+            nt.x1c = K.rows_cut_fwd(nt.f32("x1", plan.M, D), B, L, mc[0], mc[1], D).reshape(plan.Mm, D)
+            if K.mhla_block_mlp_fwd(plan, nt.x1c) != 0:
+                nt.mlp = self._mlp_half_fwd(bs, p[10:], nt.x1c, g2, b2, plan.Mm, D, torch.bfloat16, False)
+        return nt
 
     def _bwd_native(self, bs, tp, g, g_lp):
         """The input-gradient chain of a block with a native tape as one library call, then what MLPChain.bwd,
@@ -1363,21 +1438,40 @@ class EncoderOp:
         _WG["list"] / _DEFER until those launches have been issued; nothing is freed or reused before."""
         plan = tp.plan
         g1, b1, g2, b2 = tp.ln
-        tg = [_gt(q) for q in tp.ln]
+        # (a narrowed block whose MLP half ran here hands over its arena with the two views; mhla_block_mlp_bwd has
+        # then just filled the descriptor's pointers, LayerNorm 2 has its gradient buffers, and g / g_lp come from
+        # the row cut in EncoderOp.bwd)
+        handed, tp.arena = tp.arena, None
+        tg = [_gt(g1), _gt(b1)] if handed is not None else [_gt(q) for q in tp.ln]
         if any(t is None for t in tg):
             return None
         M, D, Hd = plan.M, plan.D, plan.hidden
-        if (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (M, D) or not g.is_contiguous()
-                or tuple(g_lp.shape) != (M, D) or not g_lp.is_contiguous()):
+        if handed is None and (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (M, D)
+                               or not g.is_contiguous() or tuple(g_lp.shape) != (M, D) or not g_lp.is_contiguous()):
             return None
         want_lp = tp.cut is None
-        arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
+        if handed is not None:
+            arena, abf, af = handed
+        else:
+            arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
         wp_c, w1_c, w2_c = tp.wc
-        if K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp) != 0:
+        if handed is not None:
+            rc = K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp, ptrs_set=True)
+        else:
+            rc = K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp)
+        if rc != 0:
             return None
         bo = plan.boff[want_lp]
-        abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
+        if handed is None:
+            abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
         part = lambda k: _carve(af, bo[k][0] // 4, (2, plan.nparts, D))
+        if tp.mcut is not None:               # the attention half of a narrowed block: g / g_lp is the expanded pair
+            dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
+            dwp, dbp = bs.attn.proj_grads(g_lp, tp.bf("o", M, D), tp.pa)
+            ga = bs.attn.qkv_grads(dqkv, tp.bf("xn1", M, D), tp.pa) + [dwp, dbp]
+            _DEFER["ln"].append((part("part1"), tg[0], tg[1], (g1, b1)))
+            g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
+            return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, None
         g1_lp = _carve(abf, bo["g1_lp"][0] // 2, (M, D))
         dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
         dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", M, Hd), tp.pm)
@@ -1389,12 +1483,39 @@ class EncoderOp:
         g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
         return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, [dw1, db1, dw2, db2]
 
+    def _bwd_native_mlp(self, bs, tp, g, g_lp):
+        """The MLP half of a narrowed block's input-gradient chain as one library call (dpre, dxn2, LayerNorm 2
+        backward on the half's rows), with the weight-gradient problems and the deferred fold MLPChain.bwd and ln_bwd
+        queue.  Returns (gradient of x1 on the half's rows, mlp grads) or None (then the Python chain runs the half).
+        The arena is the block's: _bwd_native issues the attention half into it after the row cut."""
+        plan = tp.plan
+        g1, b1, g2, b2 = tp.ln
+        tg2, tb2 = _gt(g2), _gt(b2)
+        if tg2 is None or tb2 is None or tp.mlp is not None:
+            return None
+        Mm, D, Hd = plan.Mm, plan.D, plan.hidden
+        if (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (Mm, D) or not g.is_contiguous()
+                or tuple(g_lp.shape) != (Mm, D) or not g_lp.is_contiguous()):
+            return None
+        want_lp = tp.cut is None
+        arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
+        wp_c, w1_c, w2_c = tp.wc
+        if K.mhla_block_mlp_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, tp.x1c, g, g_lp, arena, want_lp) != 0:
+            return None
+        bo = plan.boff[want_lp]
+        abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
+        tp.arena = (arena, abf, af)
+        dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", Mm, Hd), tp.pm)
+        dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (Mm, Hd)), tp.bf("xn2", Mm, D), tp.pm)
+        _DEFER["ln"].append((_carve(af, bo["part2"][0] // 4, (2, plan.nparts2, D)), tg2, tb2, (g2, b2)))
+        return _carve(af, bo["g1_f32"][0] // 4, (Mm, D)), [dw1, db1, dw2, db2]
+
     def bwd(self, saved, dy, needs):
         tapes, B, L, D = saved
         g = dy.reshape(-1, D)
         g_lp = _as_cdt(g)
         grads = []
-        begin_wgrads(per_block=any(_tape_cut(tp) is not None for tp in tapes))
+        begin_wgrads(per_block=any(_tape_cut(tp) is not None or _tape_mcut(tp) is not None for tp in tapes))
         begin_deferred()
         begin_zero_pool(sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)), dy.device)
 
@@ -1429,28 +1550,55 @@ class EncoderOp:
                     nbs, ntp = order[bi + 1]
                     pd_n = nbs.mlp.out_dropout(ntp[9])
                     q8n = _q8_request(nbs.mlp, ntp[10][1], "bwd", D)       # the next block's fc2 input-gradient GEMM
-                done = None
-                if isinstance(tp, _NativeTape):
-                    if not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"] and _native_blocks_on():
-                        done = self._bwd_native(bs, tp, g, g_lp)
-                    if done is None:
-                        tp = tp.unpack()
+                rows_tp = tp
+                nat_ok = (isinstance(tp, _NativeTape) and not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"]
+                          and _native_blocks_on())
+                narrowed = isinstance(tp, _NativeTape) and tp.mcut is not None
+                done = self._bwd_native(bs, tp, g, g_lp) if nat_ok and not narrowed else None
                 if done is not None:
                     g, g_lp, ga, gm = done
                     dg1 = db1 = dg2 = db2 = None
                     cut, lp_dt = tp.cut, torch.bfloat16
                 else:
-                    x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa_, _), cut = tp
-                    dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
-                    pd = bs.attn.out_dropout(sa) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
-                    # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
-                    # written, since a branch with output dropout gets it pre-masked)
-                    g, g_lp, dg2, db2 = ln_bwd(dxn2, x1, g2, b2, mu2, rs2, g, pd,
-                                               q8=_q8_request(bs.attn, pa_, "bwd", D) if hasattr(bs.attn, "out_dropout") else None)
-                    dxn1, ga = (bs.attn.bwd(sa, g_lp, premasked=pd[0] > 0) if hasattr(bs.attn, "out_dropout")
-                                else bs.attn.bwd(sa, g_lp))
-                    g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd_n, q8=q8n, want_lp=cut is None)
-                    lp_dt = dxn1.dtype
+                    # the two halves, each from the library (a narrowed native tape) or from the Python chains
+                    nt, tp = (tp, None) if narrowed else (None, tp.unpack() if isinstance(tp, _NativeTape) else tp)
+                    half = self._bwd_native_mlp(bs, nt, g, g_lp) if narrowed and nat_ok else None
+                    pd = (0.0, 0)
+                    if half is not None:
+                        g, gm = half
+                        g_lp, dg2, db2 = None, None, None
+                        mcut, lp_dt = nt.mcut, torch.bfloat16
+                    else:
+                        tp = tp if tp is not None else nt.unpack()
+                        x1, mu2, rs2, (g2, b2), sm, (pa_, _), mcut = tp[5], tp[6], tp[7], tp[8], tp[9], tp[10], tp[12]
+                        dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
+                        pd = bs.attn.out_dropout(tp[4]) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
+                        # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
+                        # written, since a branch with output dropout gets it pre-masked)
+                        g, g_lp, dg2, db2 = ln_bwd(dxn2, x1, g2, b2, mu2, rs2, g, pd,
+                                                   q8=_q8_request(bs.attn, pa_, "bwd", D) if hasattr(bs.attn, "out_dropout") else None,
+                                                   want_lp=mcut is None)
+                        lp_dt = dxn2.dtype
+                    if mcut is not None:
+                        # the MLP half ran on the rows the block above reads: back to this block's rows, with the copy
+                        # the proj input-gradient and weight-gradient GEMMs read written in the same pass
+                        g, g_lp = K.rows_cut_bwd(g, B, mcut[0], mcut[1], mcut[2], D, lp_dtype=lp_dt if g.dtype != lp_dt else None)
+                        g = g.reshape(B * mcut[0], D)
+                        g_lp = g_lp.reshape(B * mcut[0], D) if g_lp is not None else g
+                    half = self._bwd_native(bs, nt, g, g_lp) if narrowed and nat_ok else None
+                    if half is not None:
+                        g, g_lp, ga, _ = half
+                        dg1 = db1 = None
+                        cut = nt.cut
+                    else:
+                        tp = tp if tp is not None else nt.unpack()
+                        x, mu1, rs1, (g1, b1), sa, cut = tp[0], tp[1], tp[2], tp[3], tp[4], tp[11]
+                        dxn1, ga = (bs.attn.bwd(sa, g_lp, premasked=pd[0] > 0) if hasattr(bs.attn, "out_dropout")
+                                    else bs.attn.bwd(sa, g_lp))
+                        g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd_n, q8=q8n, want_lp=cut is None)
+                        lp_dt = dxn1.dtype
+                    if nt is not None:
+                        nt.arena = None
                 premasked = pd_n[0] > 0
                 if cut is not None:
                     # this block ran on its (head, tail) rows: back to the rows of the block below, zeros in between,
@@ -1460,7 +1608,7 @@ class EncoderOp:
                     g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dt if more else None)
                     g = g.reshape(B * n_in, D)
                     g_lp = g_lp.reshape(B * n_in, D) if g_lp is not None else g
-                nxt = (_tape_rows(tp), _tape_rows(order[bi + 1][1])) if bi + 1 < len(order) else None
+                nxt = (_tape_rows(rows_tp), _tape_rows(order[bi + 1][1])) if bi + 1 < len(order) else None
                 if flush_wgrads(force=False, next_rows=nxt) and _STATE["grad_ready"] is not None:
                     flush_deferred()
                 if not _SIDE["enabled"]:

@@ -65,7 +65,14 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
 def _st():
+    """The current stream's handle.  Every wrapper asks for it (about 80 times per cfg2 step), so where torch has the
+    raw accessor it is used: no Stream object is built (1 us instead of 4)."""
+    if _raw_stream is not None:
+        return C.c_void_p(_raw_stream(torch.cuda.current_device()))
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -598,30 +605,46 @@ def mhla_attn_bwd(qkv, dout, B, L, H, hd, W, mask=None, p=0.0, seed=0, o=None, l
 class BlockPlan:
     """What favit_mhla_block_fwd / _bwd need for one block at one shape, kept from step to step: the descriptor with
     its geometry filled in and the two layouts (include/favit.h).  off / boff map slot names to (byte offset, bytes);
-    boff and bwd_bytes are indexed by want_lp_out (0: a row cut follows the block's backward)."""
-    __slots__ = ("desc", "ref", "M", "D", "hidden", "B", "n", "H", "nparts", "tape_bytes", "off", "bwd_bytes", "boff")
+    boff and bwd_bytes are indexed by want_lp_out (0: a row cut follows the block's backward).
+    Narrowed plans (n_mlp < n: the MLP half runs on fewer rows) also carry the companion struct
+    (rows / rref); Mm = B * n_mlp and nparts2 belong to the MLP half's slots (equal to M and nparts otherwise); st is
+    the stream of the first call of a pair of halves, which the second one reuses."""
+    __slots__ = ("desc", "ref", "M", "D", "hidden", "B", "n", "H", "nparts", "tape_bytes", "off", "bwd_bytes", "boff",
+                 "n_mlp", "Mm", "nparts2", "rows", "rref", "st")
 
 
-def mhla_block_plan(B, n, D, H, W, hidden, training, eps=1e-5) -> Optional[BlockPlan]:
+def mhla_block_plan(B, n, D, H, W, hidden, training, eps=1e-5, n_mlp=None) -> Optional[BlockPlan]:
     """The layout queries for one block geometry (host arithmetic, once per shape), or None where the native chain
-    does not take it (D / H != 64, hidden not a multiple of 8, a row count the lse attention kernels decline)."""
+    does not take it (D / H != 64, hidden not a multiple of 8, a row count the lse attention kernels decline).
+    n_mlp: rows per image of the MLP half where that is narrower than n (the two-row-count layouts)."""
     d = _abi.BlockDesc()
     d.B, d.n, d.D, d.H, d.W, d.hidden, d.training, d.eps = B, n, D, H, W, hidden, int(bool(training)), eps
     lib = _abi.lib()
+    narrow = n_mlp is not None and n_mlp != n
+    p = BlockPlan()
+    p.rows = p.rref = p.st = None
+    if narrow:
+        p.rows = _abi.BlockMlp()
+        p.rows.n_mlp = n_mlp
+        p.rref = C.byref(p.rows)
     to = (C.c_int64 * len(_abi.BLOCK_TAPE_SLOTS))()
-    tape_bytes = lib.favit_mhla_block_tape_layout(C.byref(d), to)
+    tape_bytes = (lib.favit_mhla_block_tape_layout2(C.byref(d), p.rref, to) if narrow
+                  else lib.favit_mhla_block_tape_layout(C.byref(d), to))
     if tape_bytes < 0:
         return None
-    p = BlockPlan()
     p.desc, p.ref, p.M, p.D, p.hidden, p.B, p.n, p.H = d, C.byref(d), B * n, D, hidden, B, n, H
+    p.n_mlp = n_mlp if narrow else n
+    p.Mm = B * p.n_mlp
     p.nparts = int(min(2048, (B * n + 3) // 4))
+    p.nparts2 = int(min(2048, (p.Mm + 3) // 4))
     p.tape_bytes = d.tape_bytes = tape_bytes
     ends = list(to[1:]) + [tape_bytes]
     p.off = {k: (to[i], ends[i] - to[i]) for i, k in enumerate(_abi.BLOCK_TAPE_SLOTS)}
     p.bwd_bytes, p.boff = [], []
     for want_lp in (0, 1):
         bo = (C.c_int64 * len(_abi.BLOCK_BWD_SLOTS))()
-        nb = lib.favit_mhla_block_bwd_layout(C.byref(d), want_lp, bo)
+        nb = (lib.favit_mhla_block_bwd_layout2(C.byref(d), p.rref, want_lp, bo) if narrow
+              else lib.favit_mhla_block_bwd_layout(C.byref(d), want_lp, bo))
         ends = list(bo[1:]) + [nb]
         p.bwd_bytes.append(nb)
         p.boff.append({k: (bo[i], ends[i] - bo[i]) for i, k in enumerate(_abi.BLOCK_BWD_SLOTS)})
@@ -637,25 +660,64 @@ def _block_code(code: int, what: str) -> int:
 
 
 def mhla_block_fwd(plan: BlockPlan, x, tape, g1, b1, g2, b2, weff, beff, wproj, bproj, wfc1, bfc1, wfc2, bfc2) -> int:
-    """The forward chain of one block (favit_mhla_block_fwd) on the current stream.  tape: uint8 device tensor of
-    plan.tape_bytes.  All pointers of the descriptor are rewritten (they may change from step to step); the geometry
-    and the layout stay.  Returns 0 or the code of a declined call."""
+    """The forward chain of one block (favit_mhla_block_fwd) on the current stream -- of a narrowed plan its attention
+    half (favit_mhla_block_attn_fwd: x1 is in the tape afterwards; mhla_block_mlp_fwd follows the row cut).  tape:
+    uint8 device tensor of plan.tape_bytes.  All pointers of the descriptor are rewritten (they may change from step
+    to step); the geometry and the layout stay.  Returns 0 or the code of a declined call."""
     d = plan.desc
     d.x, d.tape, d.tape_bytes = x.data_ptr(), tape.data_ptr(), tape.numel()
     d.g1, d.b1, d.g2, d.b2 = g1.data_ptr(), b1.data_ptr(), g2.data_ptr(), b2.data_ptr()
     d.weff, d.beff, d.wproj, d.bproj = weff.data_ptr(), beff.data_ptr(), wproj.data_ptr(), bproj.data_ptr()
     d.wfc1, d.bfc1, d.wfc2, d.bfc2 = wfc1.data_ptr(), bfc1.data_ptr(), wfc2.data_ptr(), bfc2.data_ptr()
+    if plan.rows is not None:
+        plan.st = _st()
+        return _block_code(_abi.lib().favit_mhla_block_attn_fwd(plan.ref, plan.rref, plan.st), "favit_mhla_block_attn_fwd")
     return _block_code(_abi.lib().favit_mhla_block_fwd(plan.ref, _st()), "favit_mhla_block_fwd")
 
 
-def mhla_block_bwd(plan: BlockPlan, x, tape, g1, g2, weff, wproj, wfc1, wfc2, g, g_lp, arena, want_lp_out: bool) -> int:
-    """The input-gradient chain of one block (favit_mhla_block_bwd).  g / g_lp: gradient of the block's output, fp32 and
-    bf16 [M, D]; arena: uint8 device tensor of plan.bwd_bytes[want_lp_out].  Only the pointers the chain reads are
-    rewritten (the biases are not read).  Returns 0 or the code of a declined call."""
+def mhla_block_mlp_fwd(plan: BlockPlan, x1c) -> int:
+    """The MLP half of a narrowed plan's forward (favit_mhla_block_mlp_fwd) on x1c fp32 [B * n_mlp, D], the cut copy of
+    the x1 that mhla_block_fwd left in the tape.  The descriptor is the one that call filled: nothing is looked up or
+    allocated here, and the stream is the one of that call (the two run in one frame of EncoderOp.fwd).  Returns 0 or
+    the code of a declined call."""
+    plan.rows.x1c = x1c.data_ptr()
+    return _block_code(_abi.lib().favit_mhla_block_mlp_fwd(plan.ref, plan.rref, plan.st), "favit_mhla_block_mlp_fwd")
+
+
+def _block_bwd_ptrs(plan, x, tape, g1, g2, weff, wproj, wfc1, wfc2):
     d = plan.desc
     d.x, d.tape, d.tape_bytes = x.data_ptr(), tape.data_ptr(), tape.numel()
     d.g1, d.g2 = g1.data_ptr(), g2.data_ptr()
     d.weff, d.wproj, d.wfc1, d.wfc2 = weff.data_ptr(), wproj.data_ptr(), wfc1.data_ptr(), wfc2.data_ptr()
+
+
+def mhla_block_mlp_bwd(plan: BlockPlan, x, tape, g1, g2, weff, wproj, wfc1, wfc2, x1c, g, g_lp, arena,
+                       want_lp_out: bool) -> int:
+    """The MLP half of a narrowed plan's input-gradient chain (favit_mhla_block_mlp_bwd).  g / g_lp: gradient of the
+    block's output, fp32 and bf16 [B * n_mlp, D].  Leaves g1_f32 [B * n_mlp, D] in the arena (plan.boff); the caller
+    expands it (rows_cut_bwd) and hands the pair to mhla_block_bwd with the same arena and want_lp_out."""
+    _block_bwd_ptrs(plan, x, tape, g1, g2, weff, wproj, wfc1, wfc2)
+    plan.rows.x1c = x1c.data_ptr()
+    plan.st = _st()
+    return _block_code(_abi.lib().favit_mhla_block_mlp_bwd(plan.ref, plan.rref, g.data_ptr(), g_lp.data_ptr(),
+                                                           arena.data_ptr(), arena.numel(), int(bool(want_lp_out)), plan.st),
+                       "favit_mhla_block_mlp_bwd")
+
+
+def mhla_block_bwd(plan: BlockPlan, x, tape, g1, g2, weff, wproj, wfc1, wfc2, g, g_lp, arena, want_lp_out: bool,
+                   ptrs_set: bool = False) -> int:
+    """The input-gradient chain of one block (favit_mhla_block_bwd).  g / g_lp: gradient of the block's output, fp32 and
+    bf16 [M, D]; arena: uint8 device tensor of plan.bwd_bytes[want_lp_out].  Only the pointers the chain reads are
+    rewritten (the biases are not read).  Returns 0 or the code of a declined call.
+    A narrowed plan: the attention half (favit_mhla_block_attn_bwd); g / g_lp are then the gradient of x1, expanded to
+    [M, D] by the row cut that follows mhla_block_mlp_bwd (ptrs_set: that call has just written the same pointers
+    into the descriptor and taken the stream, and nothing has used the plan since)."""
+    if not ptrs_set:
+        _block_bwd_ptrs(plan, x, tape, g1, g2, weff, wproj, wfc1, wfc2)
+    if plan.rows is not None:
+        return _block_code(_abi.lib().favit_mhla_block_attn_bwd(plan.ref, plan.rref, g.data_ptr(), g_lp.data_ptr(),
+                                                                arena.data_ptr(), arena.numel(), int(bool(want_lp_out)),
+                                                                plan.st if ptrs_set else _st()), "favit_mhla_block_attn_bwd")
     return _block_code(_abi.lib().favit_mhla_block_bwd(plan.ref, g.data_ptr(), g_lp.data_ptr(), arena.data_ptr(),
                                                        arena.numel(), int(bool(want_lp_out)), _st()),
                        "favit_mhla_block_bwd")

@@ -122,7 +122,13 @@ def run_encoder(blocks, x, mask, training, cls_only=False):
             prm += params(b, s.names)
         if i:
             x = F.note_segment_boundary(x)        # the next node starts a fresh autograd graph at a leaf copy of x
-        x = F.run(F.EncoderOp(specs, m, training, cuts=None if cuts is None else cuts[i:i + per]), [x], prm)
+        seg = mseg = None
+        if cuts is not None:
+            seg = cuts[i:i + per]
+            if F.mlp_narrow_on():
+                # each block's MLP half runs on the rows the next block reads; the node's last block learns them here
+                mseg = F.mlp_narrow_plan(seg, after=cuts[i + per] if i + per < len(cuts) else None)
+        x = F.run(F.EncoderOp(specs, m, training, cuts=seg, mlp_cuts=mseg), [x], prm)
     return x
 
 

@@ -508,6 +508,38 @@ int favit_mhla_block_fwd(const favit_mhla_block_t* desc, void* stream);
 int favit_mhla_block_bwd(const favit_mhla_block_t* desc, const float* g_f32, const void* g_lp, void* bwd_buffers,
                          int64_t bwd_bytes, int32_t want_lp_out, void* stream);
 
+/* The same block in two halves with a row cut between them (additive in ABI 8).  In a CLS-only
+ * encoder the next block reads n_mlp <= n rows per image of this block's output, and everything after proj is
+ * row-wise, so the MLP half (LN2, fc1, fc2 + residual and their backward) runs on B * n_mlp rows:
+ *   attn_fwd (LN1, qkv, attention, proj + residual on B * n rows; x1 lands in the tape)
+ *   -> the caller cuts x1 to x1c fp32 [B * n_mlp, D] (favit_rows_cut_fwd) -> mlp_fwd (x2 fp32 [B * n_mlp, D])
+ *   mlp_bwd (dpre, dxn2, LayerNorm 2 backward: g1_f32 on B * n_mlp rows)
+ *   -> the caller expands g1_f32 to B * n rows, fp32 and bf16 (favit_rows_cut_bwd) -> attn_bwd (g_out on B * n rows)
+ * The four calls of a block share its descriptor and ONE tape / ONE bwd allocation, carved by the two queries below:
+ * the slots and their order are those above, with xn2, mu2, rs2, h, pre, x2 and dpre, dxn2, g1_f32, part2 sized by
+ * Mm = B * n_mlp (part2: nparts = min(2048, (Mm + 3) / 4)), every other slot by M = B * n, and g1_lp empty when
+ * n_mlp < n (the row cut writes that copy into memory of the caller's).  n_mlp == n reproduces the offsets of
+ * favit_mhla_block_tape_layout / _bwd_layout; n_mlp <= 0 or n_mlp > n is FAVIT_ERR_INVALID.  x1c is read by mlp_fwd
+ * and mlp_bwd only (non-NULL, 16-byte aligned; it has to outlive mlp_bwd).  Validation is that of fwd / bwd: on a
+ * negative return other than FAVIT_ERR_LAUNCH nothing has been launched. */
+typedef struct favit_mhla_block_mlp {
+  const float* x1c;     /* fp32 [B * n_mlp, D]: the kept rows of x1 */
+  int32_t n_mlp;        /* rows per image of the MLP half, 1 .. n */
+  int32_t reserved;
+} favit_mhla_block_mlp_t;
+int64_t favit_mhla_block_tape_layout2(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows,
+                                      int64_t* offsets_out /* [13] or NULL */);
+int64_t favit_mhla_block_bwd_layout2(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows,
+                                     int32_t want_lp_out, int64_t* offsets_out /* [11] or NULL */);
+int favit_mhla_block_attn_fwd(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows, void* stream);
+int favit_mhla_block_mlp_fwd(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows, void* stream);
+/* g_f32 / g_lp: the gradient of x2, fp32 and bf16 [B * n_mlp, D]. */
+int favit_mhla_block_mlp_bwd(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows, const float* g_f32,
+                             const void* g_lp, void* bwd_buffers, int64_t bwd_bytes, int32_t want_lp_out, void* stream);
+/* g1_f32 / g1_lp: the gradient of x1 expanded to [B * n, D], fp32 and bf16 (zeros in the cut rows). */
+int favit_mhla_block_attn_bwd(const favit_mhla_block_t* desc, const favit_mhla_block_mlp_t* rows, const float* g1_f32,
+                              const void* g1_lp, void* bwd_buffers, int64_t bwd_bytes, int32_t want_lp_out, void* stream);
+
 /* Inverted dropout with a counter-based RNG (nn.Dropout sites, models/vit.py:136,138,
  * 102, mhla.py:159); the mask is recomputed from (seed, index) in backward. */
 int favit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t seed, void* stream);
