@@ -1125,6 +1125,11 @@ class BlockSpec:
                       ("norm2.weight", "norm2.bias") + tuple("mlp." + n for n in mlp.names))
         self.n = len(self.names)
 
+    def split(self, p):
+        """(g1, b1, pa, g2, b2, pm) of the block's parameters p, which come in the order of `names`."""
+        na = len(self.attn.names)
+        return p[0], p[1], p[2:2 + na], p[2 + na], p[3 + na], p[4 + na:]
+
 
 def cls_plan(L: int, W: int, depth: int) -> List[Optional[Tuple[int, int]]]:
     """Token rows each block of an all-MHLA encoder has to compute when only row 0 (CLS) of the last block is read
@@ -1215,19 +1220,36 @@ def _carve(flat, off, shape):
     return torch.as_strided(flat, shape, tuple(reversed(st)), off)
 
 
+class _Tape:
+    """What the Python chains of one block's forward left for backward.  x / x1: input of the attention / MLP half
+    (behind cut / mcut); ln1 / ln2: (gamma, beta); sa / sm: what the two chains saved; pa / pm: their parameters.
+    cut = (n_in, head, tail): the stream was cut from n_in rows to head + tail in front of the block, mcut: the same
+    between its halves, None: no cut there.  rows: token rows (batch x rows per image) the tape holds operands for,
+    both halves together (the ratio of two blocks scales the bytes their weight-gradient operands keep alive)."""
+    __slots__ = ("x", "mu1", "rs1", "ln1", "sa", "x1", "mu2", "rs2", "ln2", "sm", "pa", "pm", "cut", "mcut", "rows")
+    native = False
+
+    def __init__(self, *fields):
+        for k, v in zip(self.__slots__, fields):
+            setattr(self, k, v)
+        self.rows = self.x.shape[0] + self.x1.shape[0]
+
+
 class _NativeTape:
     """What a native block forward left for backward: ONE device allocation (buf, carved by plan.off) plus the
-    references the Python tape tuple holds.  Tensor views of the allocation are made only when somebody asks:
-    the native backward needs four of them (the weight-gradient operands), the Python backward all (unpack)."""
-    __slots__ = ("plan", "buf", "x", "ln", "pa", "pm", "weff", "wc", "cut", "mcut", "x1c", "mlp", "arena", "_bf", "_f32")
+    references a _Tape holds, under the same names.  Tensor views of the allocation are made only when somebody asks:
+    the native backward needs four of them (the weight-gradient operands, through bf); the Python backward reads the
+    fields of _Tape, and the first one it reads of a half makes that half's views (__getattr__).
+    mcut: the MLP half ran on x1, the cut copy of the tape's x1 (held here for backward).  mlp_in_tape = False: the
+    library declined that half's call, and mu2 / rs2 / sm are what the Python chain left."""
+    __slots__ = ("plan", "buf", "x", "ln1", "ln2", "pa", "pm", "weff", "wc", "cut", "mcut", "rows", "mlp_in_tape",
+                 "mu1", "rs1", "sa", "x1", "mu2", "rs2", "sm", "_bf", "_f32")
+    native = True
 
-    def __init__(self, plan, buf, x, ln, pa, pm, weff, wc, cut, mcut=None, x1c=None, mlp=None):
-        """mcut = (n, head, tail): the MLP half ran on head + tail of the block's n rows, on x1c (the cut copy of the
-        tape's x1; held here for backward).  mlp: what the Python chain left of that half, (xn2, mu2, rs2, sm, x2),
-        where the library declined its call; None: the half is in the tape."""
-        self.plan, self.buf, self.x, self.ln, self.pa, self.pm, self.weff, self.wc, self.cut = \
-            plan, buf, x, ln, pa, pm, weff, wc, cut
-        self.mcut, self.x1c, self.mlp, self.arena = mcut, x1c, mlp, None
+    def __init__(self, plan, buf, x, ln1, ln2, pa, pm, weff, wc, cut):
+        self.plan, self.buf, self.x, self.ln1, self.ln2, self.pa, self.pm = plan, buf, x, ln1, ln2, pa, pm
+        self.weff, self.wc, self.cut, self.mcut, self.mlp_in_tape = weff, wc, cut, None, True
+        self.rows = plan.M + plan.Mm
         self._bf = self._f32 = None
 
     def bf(self, name, *shape):
@@ -1240,39 +1262,27 @@ class _NativeTape:
             self._f32 = self.buf.view(torch.float32)
         return _carve(self._f32, self.plan.off[name][0] // 4, shape)
 
-    def unpack(self):
-        """The tape tuple EncoderOp.fwd's Python path would have built for this block (EncoderOp.bwd reads it)."""
-        pl = self.plan
-        M, Mm, D, Hd = pl.M, pl.Mm, pl.D, pl.hidden
-        (g1, b1, g2, b2), (wp_c, w1_c, w2_c) = self.ln, self.wc
-        lse = self.f32("lse", pl.B, pl.H, pl.n) if pl.off["lse"][1] else None
-        sa = (self.bf("xn1", M, D), self.weff, self.bf("qkv", M, 3 * D), self.bf("o", M, D), wp_c, None, pl.B, pl.n,
-              0.0, 0, 0.0, 0, self.pa, lse)
-        if self.mlp is not None:
-            _, mu2, rs2, sm, _ = self.mlp
+    def __getattr__(self, name):
+        """Reached for a slot that is still empty: the Python backward reads one half of this tape.  Fills that half's
+        slots with what EncoderOp.fwd's Python path would have saved there, once."""
+        if name in ("mu1", "rs1", "sa"):
+            pl = self.plan
+            M, D = pl.M, pl.D
+            lse = self.f32("lse", pl.B, pl.H, pl.n) if pl.off["lse"][1] else None
+            self.sa = (self.bf("xn1", M, D), self.weff, self.bf("qkv", M, 3 * D), self.bf("o", M, D), self.wc[0], None,
+                       pl.B, pl.n, 0.0, 0, 0.0, 0, self.pa, lse)
+            self.mu1, self.rs1 = self.f32("mu1", M), self.f32("rs1", M)
+        elif name in ("x1", "mu2", "rs2", "sm"):
+            pl = self.plan
+            Mm, D, Hd = pl.Mm, pl.D, pl.hidden
+            self.sm = (self.bf("xn2", Mm, D), (self.bf("pre", Mm, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)),
+                       self.bf("h", Mm, Hd), self.wc[1], self.wc[2], 0.0, 0, 0, self.pm)
+            self.mu2, self.rs2 = self.f32("mu2", Mm), self.f32("rs2", Mm)
+            if self.mcut is None:
+                self.x1 = self.f32("x1", pl.M, D)
         else:
-            sm = (self.bf("xn2", Mm, D), (self.bf("pre", Mm, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)),
-                  self.bf("h", Mm, Hd), w1_c, w2_c, 0.0, 0, 0, self.pm)
-            mu2, rs2 = self.f32("mu2", Mm), self.f32("rs2", Mm)
-        x1 = self.x1c if self.mcut is not None else self.f32("x1", M, D)
-        return (self.x, self.f32("mu1", M), self.f32("rs1", M), (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm,
-                (self.pa, self.pm), self.cut, self.mcut)
-
-
-def _tape_cut(tp):
-    return tp.cut if isinstance(tp, _NativeTape) else tp[11]
-
-
-def _tape_mcut(tp):
-    return tp.mcut if isinstance(tp, _NativeTape) else tp[12]
-
-
-def _tape_rows(tp):
-    """Token rows (batch x rows per image) the block of this tape holds operands for: those of its attention half plus
-    those of its MLP half (the ratio of two blocks scales the bytes their weight-gradient operands keep alive)."""
-    if isinstance(tp, _NativeTape):
-        return tp.plan.M + tp.plan.Mm
-    return tp[0].shape[0] + tp[5].shape[0]
+            raise AttributeError(name)
+        return getattr(self, name)
 
 
 class EncoderOp:
@@ -1322,13 +1332,9 @@ class EncoderOp:
         native = self.mask is None and x.is_cuda and _native_blocks_on()
         off = 0
         for bi, bs in enumerate(self.blocks):
-            p = list(prm[off:off + bs.n])
+            g1, b1, pa, g2, b2, pm = p = bs.split(list(prm[off:off + bs.n]))
             off += bs.n
-            na = len(bs.attn.names)
-            g1, b1 = p[0], p[1]
-            pa = p[2:2 + na]
-            g2, b2 = p[2 + na], p[3 + na]
-            pm = p[4 + na:]
+            # 1. the cut in front of the block
             cut = None
             if self.cuts is not None and self.cuts[bi] is not None and sum(self.cuts[bi]) < L:
                 ca, cb = self.cuts[bi]
@@ -1339,38 +1345,48 @@ class EncoderOp:
             mc = self.mlp_cuts[bi] if self.mlp_cuts is not None else None
             if mc is not None and sum(mc) >= L:
                 mc = None
-            if native and pre[bi] is not None:
-                nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut, mc)
-                if nt is not None:
-                    tapes.append(nt)
-                    if mc is not None:
-                        L = sum(mc)
-                        M = B * L
-                    x = nt.f32("x2", M, D) if nt.mlp is None else nt.mlp[4]
-                    continue
-            fuse = fuse_ok and M <= 16384
-            if fuse and isinstance(bs.attn, (MHLAChain, DenseChain)):
-                o1 = [None, None, None]
-                kw = {"pre": pre[bi]} if pre[bi] is not None else {}
-                x1, sa = bs.attn.fwd(None, pa, B, L, x, self.mask, self.training, ln=(x, g1.detach(), b1.detach(), o1), **kw)
-                xn1, mu1, rs1 = o1
-            else:
-                xn1, mu1, rs1 = K.layernorm_fwd(x, D, g1, b1, M, D, cdt, q8=_q8_request(bs.attn, pa, "fwd", D))
-                if pre[bi] is not None:
-                    x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training, pre=pre[bi])
-                else:
-                    x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training)
+            # 2. the attention half, x1 = x + attn(LN1(x)) (the library runs a block without an inner cut whole)
+            nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut, mc) if native and pre[bi] is not None else None
+            if nt is None:
+                x1, mu1, rs1, sa = self._attn_half_fwd(bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre[bi])
+            elif mc is not None:
+                x1 = nt.f32("x1", M, D)
+            # 3. the cut between the halves, to the rows the next block reads: everything from here on is row-wise
             mcut = None
             if mc is not None:
-                # the rows the next block reads: everything from here on is row-wise, so the cut comes first
                 x1 = K.rows_cut_fwd(x1, B, L, mc[0], mc[1], D).reshape(B * sum(mc), D)
                 mcut = (L, mc[0], mc[1])
                 L = sum(mc)
                 M = B * L
-            xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
-            tapes.append((x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, (pa, pm), cut, mcut))
-            x = x2
+            # 4. the MLP half, x2 = x1 + mlp(LN2(x1)), and the block's tape
+            if nt is None:
+                xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
+                tapes.append(_Tape(x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, pa, pm, cut, mcut))
+                x = x2
+                continue
+            if mcut is not None:
+                # the second call on the descriptor the attention half filled; where the library declines it, the
+                # Python chain runs the half and the tape holds its tensors
+                nt.mcut, nt.x1 = mcut, x1
+                if K.mhla_block_mlp_fwd(nt.plan, x1) != 0:
+                    nt.mlp_in_tape = False
+                    _, nt.mu2, nt.rs2, nt.sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
+            tapes.append(nt)
+            x = nt.f32("x2", M, D) if nt.mlp_in_tape else x2
         return x.reshape(B, L, D), (tapes, B, L_in, D)
+
+    def _attn_half_fwd(self, bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre):
+        """LayerNorm 1 and the attention chain on the B * L rows of x (the Python chains)."""
+        M = B * L
+        kw = {"pre": pre} if pre is not None else {}
+        if fuse_ok and M <= 16384 and isinstance(bs.attn, (MHLAChain, DenseChain)):
+            o1 = [None, None, None]
+            x1, sa = bs.attn.fwd(None, pa, B, L, x, self.mask, self.training, ln=(x, g1.detach(), b1.detach(), o1), **kw)
+            xn1, mu1, rs1 = o1
+        else:
+            xn1, mu1, rs1 = K.layernorm_fwd(x, D, g1, b1, M, D, cdt, q8=_q8_request(bs.attn, pa, "fwd", D))
+            x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training, **kw)
+        return x1, mu1, rs1, sa
 
     def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, fuse_ok):
         """LayerNorm 2 and the MLP chain on the M rows of x1 (the Python chains)."""
@@ -1383,19 +1399,20 @@ class EncoderOp:
             x2, sm = bs.mlp.fwd(xn2, pm, x1, self.training)
         return xn2, mu2, rs2, sm, x2
 
-    def _fwd_native(self, bs, p, x, B, L, D, pre, cut, mc=None):
+    def _fwd_native(self, bs, p, x, B, L, D, pre, cut, mc):
         """One block's forward as one library call, or None where this block runs the Python chains: not MHLA + MLP, a
         dropout that is active in this mode, parameters of another dtype or shape than the chain assumes, a geometry
         the library declines (favit_mhla_block_tape_layout), or a declined call (nothing was launched then).
-        mc = (head, tail): the MLP half runs on those rows -- the attention half as one call, the Python-visible row
-        cut of x1, then the MLP half as a second call on the same descriptor (where the library declines that one,
-        the Python chain runs the half and the tape holds its tensors)."""
+        p: BlockSpec.split of the block's parameters.  mc = (head, tail): the MLP half will run on those rows -- this
+        call is the attention half then (x1 is in the tape), and EncoderOp.fwd follows with the Python-visible row cut
+        of x1 and the MLP half as a second call on the same descriptor."""
         at, ml = bs.attn, bs.mlp
-        if not (isinstance(at, MHLAChain) and isinstance(ml, MLPChain)) or len(p) != 14:
+        g1, b1, pa, g2, b2, pm = p
+        if not (isinstance(at, MHLAChain) and isinstance(ml, MLPChain)) or (len(pa), len(pm)) != (len(at.names), len(ml.names)):
             return None
         if self.training and (at.p_attn > 0 or at.p_proj > 0 or ml.p > 0):
             return None
-        g1, b1, wqkv, bqkv, wl, bl, wp, bp, g2, b2, w1, c1, w2, c2 = p
+        (wqkv, bqkv, wl, bl, wp, bp), (w1, c1, w2, c2) = pa, pm
         Hd = w1.shape[0]
         if tuple(w2.shape) != (D, Hd) or tuple(w1.shape) != (Hd, D) or tuple(wp.shape) != (D, D):
             return None
@@ -1421,77 +1438,62 @@ class EncoderOp:
         buf = torch.empty(plan.tape_bytes, dtype=torch.uint8, device=x.device)
         if K.mhla_block_fwd(plan, x, buf, g1, b1, g2, b2, weff, beff, wc[0], bp, wc[1], c1, wc[2], c2) != 0:
             return None
-        nt = _NativeTape(plan, buf, x, (g1, b1, g2, b2), p[2:8], p[10:], weff, wc, cut)
-        if mc is not None:
-            nt.mcut = (L, mc[0], mc[1])
-            nt.x1c = K.rows_cut_fwd(nt.f32("x1", plan.M, D), B, L, mc[0], mc[1], D).reshape(plan.Mm, D)
-            if K.mhla_block_mlp_fwd(plan, nt.x1c) != 0:
-                nt.mlp = self._mlp_half_fwd(bs, p[10:], nt.x1c, g2, b2, plan.Mm, D, torch.bfloat16, False)
-        return nt
+        return _NativeTape(plan, buf, x, (g1, b1), (g2, b2), pa, pm, weff, wc, cut)
 
-    def _bwd_native(self, bs, tp, g, g_lp):
-        """The input-gradient chain of a block with a native tape as one library call, then what MLPChain.bwd,
-        MHLAChain.bwd and ln_bwd do besides launching it: the weight-gradient problems and the deferred folds, in
-        their order.  Returns (g, g_lp or None, attention grads, mlp grads), or None where the Python chains have to run
-        (a LayerNorm parameter without a gradient buffer, a gradient of another layout, a declined call).
+    def _bwd_native(self, bs, tp, g, g_lp, handed=None):
+        """The input-gradient chain of a block with a native tape as one library call -- of a narrowed block
+        (tp.mcut) its attention half, g / g_lp being the expanded gradient of x1 -- then what MLPChain.bwd,
+        MHLAChain.bwd and _ln_bwd do besides launching it: the weight-gradient problems and the deferred folds, in
+        their order.  Returns (g, g_lp or None, attention grads, mlp grads or None for a half), or None where the
+        Python chains have to run (a LayerNorm parameter without a gradient buffer, a gradient of another layout, a
+        declined call).
+        handed = (arena, its bf16 view, its fp32 view) from _bwd_native_mlp: that call was taken on tp.plan in this
+        iteration of EncoderOp.bwd and only the row cut came since, so the descriptor holds this block's pointers and
+        the stream (ptrs_set), LayerNorm 2 has its gradient buffers, and g / g_lp come from the row cut.  Plans are
+        shared by every tape of one shape: in any other case the pointers have to be written again.
         Lifetime: every buffer the queued launches read or write is a VIEW of the arena or of the tape, held by
         _WG["list"] / _DEFER until those launches have been issued; nothing is freed or reused before."""
         plan = tp.plan
-        g1, b1, g2, b2 = tp.ln
-        # (a narrowed block whose MLP half ran here hands over its arena with the two views; mhla_block_mlp_bwd has
-        # then just filled the descriptor's pointers, LayerNorm 2 has its gradient buffers, and g / g_lp come from
-        # the row cut in EncoderOp.bwd)
-        handed, tp.arena = tp.arena, None
-        tg = [_gt(g1), _gt(b1)] if handed is not None else [_gt(q) for q in tp.ln]
+        g1, g2 = tp.ln1[0], tp.ln2[0]
+        tg = [_gt(q) for q in (tp.ln1 if handed is not None else tp.ln1 + tp.ln2)]
         if any(t is None for t in tg):
             return None
         M, D, Hd = plan.M, plan.D, plan.hidden
+        want_lp = tp.cut is None
         if handed is None and (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (M, D)
                                or not g.is_contiguous() or tuple(g_lp.shape) != (M, D) or not g_lp.is_contiguous()):
             return None
-        want_lp = tp.cut is None
-        if handed is not None:
-            arena, abf, af = handed
-        else:
-            arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
-        wp_c, w1_c, w2_c = tp.wc
-        if handed is not None:
-            rc = K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp, ptrs_set=True)
-        else:
-            rc = K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, g, g_lp, arena, want_lp)
-        if rc != 0:
+        arena, abf, af = handed or (torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device), None, None)
+        if K.mhla_block_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, *tp.wc, g, g_lp, arena, want_lp,
+                            ptrs_set=handed is not None) != 0:
             return None
         bo = plan.boff[want_lp]
         if handed is None:
             abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
         part = lambda k: _carve(af, bo[k][0] // 4, (2, plan.nparts, D))
-        if tp.mcut is not None:               # the attention half of a narrowed block: g / g_lp is the expanded pair
-            dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
-            dwp, dbp = bs.attn.proj_grads(g_lp, tp.bf("o", M, D), tp.pa)
-            ga = bs.attn.qkv_grads(dqkv, tp.bf("xn1", M, D), tp.pa) + [dwp, dbp]
-            _DEFER["ln"].append((part("part1"), tg[0], tg[1], (g1, b1)))
-            g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
-            return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, None
-        g1_lp = _carve(abf, bo["g1_lp"][0] // 2, (M, D))
+        gm = None
+        if tp.mcut is None:                   # the whole block: its MLP half's problems and fold come first
+            dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", M, Hd), tp.pm)
+            dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (M, Hd)), tp.bf("xn2", M, D), tp.pm)
+            _DEFER["ln"].append((part("part2"), tg[2], tg[3], tp.ln2))
+            gm = [dw1, db1, dw2, db2]
+            g_lp = _carve(abf, bo["g1_lp"][0] // 2, (M, D))         # the gradient of x1 the call left
         dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
-        dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", M, Hd), tp.pm)
-        dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (M, Hd)), tp.bf("xn2", M, D), tp.pm)
-        _DEFER["ln"].append((part("part2"), tg[2], tg[3], (g2, b2)))
-        dwp, dbp = bs.attn.proj_grads(g1_lp, tp.bf("o", M, D), tp.pa)
+        dwp, dbp = bs.attn.proj_grads(g_lp, tp.bf("o", M, D), tp.pa)
         ga = bs.attn.qkv_grads(dqkv, tp.bf("xn1", M, D), tp.pa) + [dwp, dbp]
-        _DEFER["ln"].append((part("part1"), tg[0], tg[1], (g1, b1)))
+        _DEFER["ln"].append((part("part1"), tg[0], tg[1], tp.ln1))
         g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
-        return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, [dw1, db1, dw2, db2]
+        return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, gm
 
     def _bwd_native_mlp(self, bs, tp, g, g_lp):
         """The MLP half of a narrowed block's input-gradient chain as one library call (dpre, dxn2, LayerNorm 2
-        backward on the half's rows), with the weight-gradient problems and the deferred fold MLPChain.bwd and ln_bwd
-        queue.  Returns (gradient of x1 on the half's rows, mlp grads) or None (then the Python chain runs the half).
-        The arena is the block's: _bwd_native issues the attention half into it after the row cut."""
+        backward on the half's rows), with the weight-gradient problems and the deferred fold MLPChain.bwd and _ln_bwd
+        queue.  Returns what _mlp_half_bwd returns, or None (then the Python chain runs the half).  handed: the block's
+        arena with its two views, for _bwd_native to issue the attention half into after the row cut."""
         plan = tp.plan
-        g1, b1, g2, b2 = tp.ln
-        tg2, tb2 = _gt(g2), _gt(b2)
-        if tg2 is None or tb2 is None or tp.mlp is not None:
+        g1, g2 = tp.ln1[0], tp.ln2[0]
+        tg2, tb2 = _gt(g2), _gt(tp.ln2[1])
+        if tg2 is None or tb2 is None or not tp.mlp_in_tape:
             return None
         Mm, D, Hd = plan.Mm, plan.D, plan.hidden
         if (g.dtype != torch.float32 or g_lp.dtype != torch.bfloat16 or tuple(g.shape) != (Mm, D) or not g.is_contiguous()
@@ -1499,43 +1501,82 @@ class EncoderOp:
             return None
         want_lp = tp.cut is None
         arena = torch.empty(plan.bwd_bytes[want_lp], dtype=torch.uint8, device=g.device)
-        wp_c, w1_c, w2_c = tp.wc
-        if K.mhla_block_mlp_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, wp_c, w1_c, w2_c, tp.x1c, g, g_lp, arena, want_lp) != 0:
+        if K.mhla_block_mlp_bwd(plan, tp.x, tp.buf, g1, g2, tp.weff, *tp.wc, tp.x1, g, g_lp, arena, want_lp) != 0:
             return None
         bo = plan.boff[want_lp]
         abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
-        tp.arena = (arena, abf, af)
         dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", Mm, Hd), tp.pm)
         dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (Mm, Hd)), tp.bf("xn2", Mm, D), tp.pm)
-        _DEFER["ln"].append((_carve(af, bo["part2"][0] // 4, (2, plan.nparts2, D)), tg2, tb2, (g2, b2)))
-        return _carve(af, bo["g1_f32"][0] // 4, (Mm, D)), [dw1, db1, dw2, db2]
+        _DEFER["ln"].append((_carve(af, bo["part2"][0] // 4, (2, plan.nparts2, D)), tg2, tb2, tp.ln2))
+        g1_f32 = _carve(af, bo["g1_f32"][0] // 4, (Mm, D))
+        return g1_f32, None, [None, None], [dw1, db1, dw2, db2], torch.bfloat16, (arena, abf, af)
+
+    @staticmethod
+    def _ln_bwd(dxn, xin, ln, mu, rs, dres, pd, q8=None, want_lp=True):
+        """LayerNorm backward of the stream; the dgamma / dbeta fold joins the deferred batch when the parameters own
+        gradient buffers (the fused-optimizer flow).  q8: the low-precision copy also leaves quantised (fp8 mode).
+        want_lp=False: a row cut follows, and favit_rows_cut_bwd writes the copy of the expanded gradient."""
+        gam, bet = ln
+        M, D = xin.shape
+        if not gam.requires_grad and not bet.requires_grad:      # frozen layer: no dgamma / dbeta fold at all
+            return K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, lp_drop=pd, frozen=True, q8=q8)
+        tg_, tb_ = _gt(gam), _gt(bet)
+        lst = _DEFER["ln"] if (_DEFER["on"] and tg_ is not None and tb_ is not None) else None
+        n0 = len(lst) if lst is not None else 0
+        out = K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, dg_out=tg_, db_out=tb_,
+                              lp_drop=pd, defer=lst, q8=q8)
+        if lst is not None:
+            lst[n0] = lst[n0] + ((gam, bet),)
+        elif out[2] is None:
+            _ready(gam, bet)
+        return out
+
+    def _mlp_half_bwd(self, bs, tp, g, g_lp, premasked, nat_ok):
+        """Backward of x2 = x1 + mlp(LN2(x1)) on the half's rows, from the library (a narrowed native tape that holds
+        the half) or from the Python chain.  Returns (gradient of x1, its low-precision copy or None where the row cut
+        that follows writes it, [dgamma2, dbeta2], the chain's parameter gradients, the dtype of that copy, and the
+        arena for _bwd_native where the library took the call, else None)."""
+        done = self._bwd_native_mlp(bs, tp, g, g_lp) if nat_ok and tp.mcut is not None else None
+        if done is not None:
+            return done
+        dxn2, gm = bs.mlp.bwd(tp.sm, g_lp, premasked=premasked)
+        # the mask of the attention branch's output dropout (a native forward had none: its attention views stay
+        # unmade); fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
+        # written, since a branch with output dropout gets it pre-masked
+        pd = (0.0, 0) if tp.native else bs.attn.out_dropout(tp.sa)
+        g, g_lp, dg2, db2 = self._ln_bwd(dxn2, tp.x1, tp.ln2, tp.mu2, tp.rs2, g, pd, want_lp=tp.mcut is None,
+                                         q8=_q8_request(bs.attn, tp.pa, "bwd", g.shape[1]))
+        return g, g_lp, [dg2, db2], gm, dxn2.dtype, None
+
+    def _attn_half_bwd(self, bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed):
+        """Backward of x1 = x + attn(LN1(x)) on the block's rows, likewise.  pd_n / q8n: what the low-precision copy
+        of the result has to carry for the block below.  Returns (gradient of x, its low-precision copy or None where
+        a row cut follows, [dgamma1, dbeta1], the chain's parameter gradients, the dtype of that copy)."""
+        done = self._bwd_native(bs, tp, g, g_lp, handed) if nat_ok and tp.mcut is not None else None
+        if done is not None:
+            g, g_lp, ga, _ = done
+            return g, g_lp, [None, None], ga, torch.bfloat16
+        sa = tp.sa
+        dxn1, ga = bs.attn.bwd(sa, g_lp, premasked=bs.attn.out_dropout(sa)[0] > 0)
+        g, g_lp, dg1, db1 = self._ln_bwd(dxn1, tp.x, tp.ln1, tp.mu1, tp.rs1, g, pd_n, q8=q8n, want_lp=tp.cut is None)
+        return g, g_lp, [dg1, db1], ga, dxn1.dtype
 
     def bwd(self, saved, dy, needs):
         tapes, B, L, D = saved
         g = dy.reshape(-1, D)
         g_lp = _as_cdt(g)
         grads = []
-        begin_wgrads(per_block=any(_tape_cut(tp) is not None or _tape_mcut(tp) is not None for tp in tapes))
+        begin_wgrads(per_block=any(tp.cut is not None or tp.mcut is not None for tp in tapes))
         begin_deferred()
         begin_zero_pool(sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)), dy.device)
 
-        def ln_bwd(dxn, xin, gam, bet, mu, rs, dres, pd, q8=None, want_lp=True):
-            """LayerNorm backward of the stream; the dgamma / dbeta fold joins the deferred batch when the parameters own
-            gradient buffers (the fused-optimizer flow).  q8: the low-precision copy also leaves quantised (fp8 mode).
-            want_lp=False: a row cut follows, and favit_rows_cut_bwd writes the copy of the expanded gradient."""
-            M = xin.shape[0]
-            if not gam.requires_grad and not bet.requires_grad:      # frozen layer: no dgamma / dbeta fold at all
-                return K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, lp_drop=pd, frozen=True, q8=q8)
-            tg_, tb_ = _gt(gam), _gt(bet)
-            lst = _DEFER["ln"] if (_DEFER["on"] and tg_ is not None and tb_ is not None) else None
-            n0 = len(lst) if lst is not None else 0
-            out = K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, dg_out=tg_, db_out=tb_,
-                                  lp_drop=pd, defer=lst, q8=q8)
-            if lst is not None:
-                lst[n0] = lst[n0] + ((gam, bet),)
-            elif out[2] is None:
-                _ready(gam, bet)
-            return out
+        def expand(g, cut, lp_dtype):
+            # back over a row cut: zeros in the rows it dropped, and the compute-dtype copy the next backward GEMMs read
+            # written in the same pass (lp_dtype; None: no copy)
+            n_in, ca, cb = cut
+            g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dtype)
+            g = g.reshape(B * n_in, D)
+            return g, (g_lp.reshape(B * n_in, D) if g_lp is not None else g)
         try:
             # The low-precision copy of the stream gradient only feeds the next branch's backward GEMMs; when that
             # branch's output was dropped in forward, the LayerNorm backward that produces the copy applies the mask
@@ -1543,77 +1584,34 @@ class EncoderOp:
             order = list(zip(reversed(self.blocks), reversed(tapes)))
             premasked = False
             for bi, (bs, tp) in enumerate(order):
+                nbs, ntp = order[bi + 1] if bi + 1 < len(order) else (None, None)
                 # what the low-precision copy of this block's input gradient has to carry for the block below
                 # (a native tape there: no dropout was active and the mode is bf16, so nothing)
                 pd_n, q8n = (0.0, 0), None
-                if bi + 1 < len(order) and not isinstance(order[bi + 1][1], _NativeTape):
-                    nbs, ntp = order[bi + 1]
-                    pd_n = nbs.mlp.out_dropout(ntp[9])
-                    q8n = _q8_request(nbs.mlp, ntp[10][1], "bwd", D)       # the next block's fc2 input-gradient GEMM
-                rows_tp = tp
-                nat_ok = (isinstance(tp, _NativeTape) and not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"]
+                if ntp is not None and not ntp.native:
+                    pd_n = nbs.mlp.out_dropout(ntp.sm)
+                    q8n = _q8_request(nbs.mlp, ntp.pm, "bwd", D)       # the next block's fc2 input-gradient GEMM
+                nat_ok = (tp.native and not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"]
                           and _native_blocks_on())
-                narrowed = isinstance(tp, _NativeTape) and tp.mcut is not None
-                done = self._bwd_native(bs, tp, g, g_lp) if nat_ok and not narrowed else None
-                if done is not None:
-                    g, g_lp, ga, gm = done
-                    dg1 = db1 = dg2 = db2 = None
-                    cut, lp_dt = tp.cut, torch.bfloat16
+                whole = self._bwd_native(bs, tp, g, g_lp) if nat_ok and tp.mcut is None else None
+                if whole is not None:         # the block without an inner cut: ONE library call
+                    (g, g_lp, ga, gm), ln1_g, ln2_g, lp_dt = whole, [None, None], [None, None], torch.bfloat16
                 else:
-                    # the two halves, each from the library (a narrowed native tape) or from the Python chains
-                    nt, tp = (tp, None) if narrowed else (None, tp.unpack() if isinstance(tp, _NativeTape) else tp)
-                    half = self._bwd_native_mlp(bs, nt, g, g_lp) if narrowed and nat_ok else None
-                    pd = (0.0, 0)
-                    if half is not None:
-                        g, gm = half
-                        g_lp, dg2, db2 = None, None, None
-                        mcut, lp_dt = nt.mcut, torch.bfloat16
-                    else:
-                        tp = tp if tp is not None else nt.unpack()
-                        x1, mu2, rs2, (g2, b2), sm, (pa_, _), mcut = tp[5], tp[6], tp[7], tp[8], tp[9], tp[10], tp[12]
-                        dxn2, gm = bs.mlp.bwd(sm, g_lp, premasked=premasked)
-                        pd = bs.attn.out_dropout(tp[4]) if hasattr(bs.attn, "out_dropout") else (0.0, 0)
-                        # (fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
-                        # written, since a branch with output dropout gets it pre-masked)
-                        g, g_lp, dg2, db2 = ln_bwd(dxn2, x1, g2, b2, mu2, rs2, g, pd,
-                                                   q8=_q8_request(bs.attn, pa_, "bwd", D) if hasattr(bs.attn, "out_dropout") else None,
-                                                   want_lp=mcut is None)
-                        lp_dt = dxn2.dtype
-                    if mcut is not None:
-                        # the MLP half ran on the rows the block above reads: back to this block's rows, with the copy
-                        # the proj input-gradient and weight-gradient GEMMs read written in the same pass
-                        g, g_lp = K.rows_cut_bwd(g, B, mcut[0], mcut[1], mcut[2], D, lp_dtype=lp_dt if g.dtype != lp_dt else None)
-                        g = g.reshape(B * mcut[0], D)
-                        g_lp = g_lp.reshape(B * mcut[0], D) if g_lp is not None else g
-                    half = self._bwd_native(bs, nt, g, g_lp) if narrowed and nat_ok else None
-                    if half is not None:
-                        g, g_lp, ga, _ = half
-                        dg1 = db1 = None
-                        cut = nt.cut
-                    else:
-                        tp = tp if tp is not None else nt.unpack()
-                        x, mu1, rs1, (g1, b1), sa, cut = tp[0], tp[1], tp[2], tp[3], tp[4], tp[11]
-                        dxn1, ga = (bs.attn.bwd(sa, g_lp, premasked=pd[0] > 0) if hasattr(bs.attn, "out_dropout")
-                                    else bs.attn.bwd(sa, g_lp))
-                        g, g_lp, dg1, db1 = ln_bwd(dxn1, x, g1, b1, mu1, rs1, g, pd_n, q8=q8n, want_lp=cut is None)
-                        lp_dt = dxn1.dtype
-                    if nt is not None:
-                        nt.arena = None
+                    g, g_lp, ln2_g, gm, lp_dt, handed = self._mlp_half_bwd(bs, tp, g, g_lp, premasked, nat_ok)
+                    if tp.mcut is not None:
+                        # the MLP half ran on the rows the block above reads: back to this block's rows
+                        g, g_lp = expand(g, tp.mcut, lp_dt if g.dtype != lp_dt else None)
+                    g, g_lp, ln1_g, ga, lp_dt = self._attn_half_bwd(bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed)
                 premasked = pd_n[0] > 0
-                if cut is not None:
-                    # this block ran on its (head, tail) rows: back to the rows of the block below, zeros in between,
-                    # with the compute-dtype copy that block's backward GEMMs read written in the same pass
-                    n_in, ca, cb = cut
-                    more = bi + 1 < len(order) and g.dtype != lp_dt
-                    g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dt if more else None)
-                    g = g.reshape(B * n_in, D)
-                    g_lp = g_lp.reshape(B * n_in, D) if g_lp is not None else g
-                nxt = (_tape_rows(rows_tp), _tape_rows(order[bi + 1][1])) if bi + 1 < len(order) else None
-                if flush_wgrads(force=False, next_rows=nxt) and _STATE["grad_ready"] is not None:
+                if tp.cut is not None:
+                    # this block ran on its (head, tail) rows: back to the rows of the block below
+                    g, g_lp = expand(g, tp.cut, lp_dt if ntp is not None and g.dtype != lp_dt else None)
+                if flush_wgrads(force=False, next_rows=(tp.rows, ntp.rows) if ntp is not None else None) \
+                        and _STATE["grad_ready"] is not None:
                     flush_deferred()
                 if not _SIDE["enabled"]:
                     join_side_stream()
-                grads = [dg1, db1] + ga + [dg2, db2] + gm + grads
+                grads = ln1_g + ga + ln2_g + gm + grads
         except BaseException:
             _WG["list"] = None                # drop the half-collected weight gradients of the failed backward
             _SIDE["pending"].clear()

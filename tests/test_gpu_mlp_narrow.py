@@ -93,9 +93,11 @@ def _encoder(favit, B, L, D, H, W, depth, seed=3):
 
 
 def _run_encoder(favit, K, monkeypatch, blocks, x0, between=None, grad_buffers=True):
-    """(output, stream gradient, LayerNorm partial sums, parameter gradients) of the CLS-only encoder."""
-    for p in blocks.parameters():
-        p.grad = torch.zeros_like(p) if grad_buffers else None
+    """(output, stream gradient, LayerNorm partial sums, parameter gradients) of the CLS-only encoder.
+    grad_buffers: True / False for all parameters, or a predicate of the parameter's name."""
+    has = grad_buffers if callable(grad_buffers) else (lambda name: grad_buffers)
+    for k, p in blocks.named_parameters():
+        p.grad = torch.zeros_like(p) if has(k) else None
     parts = []
     orig = K.reduce_rows_multi
     monkeypatch.setattr(K, "reduce_rows_multi", lambda es: (parts.extend(e[0].clone() for e in es), orig(es))[1])
@@ -238,6 +240,60 @@ def test_declined_mlp_half_calls_launch_nothing_and_the_python_half_runs(favit, 
     got = _run_encoder(favit, K, monkeypatch, blocks, x0)
     assert calls.ok["mhla_block_mlp_fwd"] == 2 and calls.n["mhla_block_mlp_bwd"] == 2 and calls.ok["mhla_block_mlp_bwd"] == 0
     assert calls.ok["mhla_block_bwd"] == 2
+    _same(got, ref, ref2)
+
+
+def test_declined_attention_half_backward_after_an_accepted_mlp_half(favit, K, env, monkeypatch):
+    """The MLP half of each narrowed block's backward is taken (its arena holds the gradient of x1), then the library
+    declines the attention half (an arena one byte short; a short tape would not do: with ptrs_set the descriptor's
+    tape pointer is not rewritten) and the Python chain runs that half on the expanded gradient.
+    Blocks 0 and 1 of this encoder are native and narrowed, block 2 (5 rows) runs the Python chains: two calls of each
+    entry point, no whole-block backward call."""
+    F = env
+    favit.set_compute_dtype("bf16")
+    blocks, x0 = _encoder(favit, *ENCODERS[0][0])
+    F.set_native_blocks(False)
+    ref = _run_encoder(favit, K, monkeypatch, blocks, x0)
+    ref2 = _run_encoder(favit, K, monkeypatch, blocks, x0)
+    F.set_native_blocks(True)
+    real = K.mhla_block_bwd
+    seen = []
+
+    def short_arena(plan, *a, **k):
+        if plan.rows is not None:
+            seen.append(k.get("ptrs_set", False))
+            a = a[:10] + (a[10][:-1],) + a[11:]
+        return real(plan, *a, **k)
+    monkeypatch.setattr(K, "mhla_block_bwd", short_arena)
+    calls = _Calls(K, monkeypatch)
+    got = _run_encoder(favit, K, monkeypatch, blocks, x0)
+    print(f"\ncalls {calls.n}, accepted {calls.ok}, ptrs_set {seen}", end="")
+    assert calls.ok["mhla_block_fwd"] == 2 and calls.ok["mhla_block_mlp_fwd"] == 2
+    assert calls.n["mhla_block_mlp_bwd"] == 2 and calls.ok["mhla_block_mlp_bwd"] == 2
+    assert calls.n["mhla_block_bwd"] == 2 and calls.ok["mhla_block_bwd"] == 0
+    assert seen == [True, True], "the attention half follows an accepted MLP half of the same plan"
+    _same(got, ref, ref2)
+
+
+def test_layernorm1_without_gradient_buffers_layernorm2_with(favit, K, env, monkeypatch):
+    """The LayerNorm 2 fold of a narrowed block goes to its gradient buffers from the native MLP half; LayerNorm 1 has
+    none, so the attention half is never offered to the library and the Python chain returns dgamma / dbeta."""
+    F = env
+    favit.set_compute_dtype("bf16")
+    blocks, x0 = _encoder(favit, *ENCODERS[0][0])
+    has = lambda name: "norm1" not in name
+    F.set_native_blocks(False)
+    ref = _run_encoder(favit, K, monkeypatch, blocks, x0, grad_buffers=has)
+    ref2 = _run_encoder(favit, K, monkeypatch, blocks, x0, grad_buffers=has)
+    F.set_native_blocks(True)
+    calls = _Calls(K, monkeypatch)
+    got = _run_encoder(favit, K, monkeypatch, blocks, x0, grad_buffers=has)
+    print(f"\ncalls {calls.n}, accepted {calls.ok}, deferred LayerNorm folds {len(got[2])} (reference {len(ref[2])})", end="")
+    assert calls.ok["mhla_block_fwd"] == 2 and calls.ok["mhla_block_mlp_fwd"] == 2
+    assert calls.n["mhla_block_mlp_bwd"] == 2 and calls.ok["mhla_block_mlp_bwd"] == 2
+    assert calls.ok["mhla_block_bwd"] == 0, "no narrowed attention-half call is accepted"
+    assert len(got[2]) == 3, "LayerNorm 2 of every block folds deferred, LayerNorm 1 of none"
+    assert all(k in got[3] for k in ref[3])
     _same(got, ref, ref2)
 
 
