@@ -66,6 +66,20 @@ class BlockMlp(C.Structure):
     _fields_ = [("x1c", vp), ("n_mlp", i32), ("reserved", i32)]
 
 
+ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN = 64, 256        # FAVIT_ADAMW_MAX_SEGMENTS / _SEG_ALIGN (checked against the library)
+
+
+class AdamwMulti(C.Structure):
+    """Mirror of favit_adamw_multi_t (include/favit.h)."""
+    _fields_ = [
+        ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("ema", vp),
+        ("n", i64), ("count", i32), ("skip_nonfinite", i32),
+        ("end", i64 * ADAMW_MAX_SEGMENTS), ("lr", f32 * ADAMW_MAX_SEGMENTS), ("weight_decay", f32 * ADAMW_MAX_SEGMENTS),
+        ("beta1", f32), ("beta2", f32), ("eps", f32), ("bias_c1", f32), ("bias_c2", f32), ("grad_scale", f32),
+        ("ema_decay", f32), ("coef", vp),
+    ]
+
+
 BLOCK_TAPE_SLOTS = ("xn1", "mu1", "rs1", "qkv", "o", "lse", "x1", "xn2", "mu2", "rs2", "h", "pre", "x2")
 BLOCK_BWD_SLOTS = ("dpre", "dxn2", "g1_f32", "g1_lp", "do", "dqkv", "dxn1", "g_out_f32", "g_out_lp", "part1", "part2")
 
@@ -151,6 +165,9 @@ _SIGS = {
     "favit_adamw_clip_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, f32, vp],
                              C.c_int),
     "favit_swap_params": ([vp, vp, vp, i64, vp], C.c_int),
+    "favit_adamw_multi": ([C.POINTER(AdamwMulti), vp], C.c_int),
+    "favit_adamw_multi_max_segments": ([], C.c_int),
+    "favit_adamw_multi_align": ([], C.c_int),
     "favit_batch_mix": ([vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
     "favit_cross_entropy_mix": ([vp, vp, vp, vp, vp, i32, i32, f32, f32, vp], C.c_int),
     "favit_randaugment_max_ops": ([], C.c_int),

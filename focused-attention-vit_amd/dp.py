@@ -58,7 +58,17 @@ class FlatBuffers:
     Order inside the buffer = reverse registration order ~ the order gradients become ready.
     """
 
-    def __init__(self, params: Iterable[torch.nn.Parameter]):
+    @staticmethod
+    def size_of(params: Iterable[torch.nn.Parameter]) -> int:
+        """Elements FlatBuffers(params) occupies: every trainable tensor rounded up to 4 elements."""
+        return sum((p.numel() + 3) // 4 * 4 for p in params if p.requires_grad)
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], flat_p: Optional[torch.Tensor] = None,
+                 flat_g: Optional[torch.Tensor] = None):
+        """flat_p / flat_g (both or neither): caller-provided storage -- two zero-filled contiguous fp32 tensors of one
+        length >= size_of(params) on the parameters' device, typically slices of a larger arena that several
+        FlatBuffers share (train.FusedAdamW(fuse_groups=True)).  The parameters fill the front, the rest is padding
+        that stays zero, and `numel` is the storage's length.  Default: buffers of exactly size_of(params)."""
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
         self.params.reverse()
         if not self.params:
@@ -71,14 +81,37 @@ class FlatBuffers:
                 raise TypeError("parameters must be fp32 masters")
             self.offsets.append(n)
             n += (p.numel() + 3) // 4 * 4          # keep every tensor 16-byte aligned
-        self.numel = n
-        self.flat_p = torch.zeros(n, dtype=dt, device=dev)
-        self.flat_g = torch.zeros(n, dtype=dt, device=dev)
+        if (flat_p is None) != (flat_g is None):
+            raise ValueError("FlatBuffers: pass both flat_p and flat_g, or neither")
+        if flat_p is None:
+            self.numel = n
+            self.flat_p = torch.zeros(n, dtype=dt, device=dev)
+            self.flat_g = torch.zeros(n, dtype=dt, device=dev)
+        else:
+            for t in (flat_p, flat_g):
+                if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+                    raise TypeError("FlatBuffers: flat_p / flat_g must be contiguous 1-d fp32 tensors on the parameters' device")
+            if flat_p.numel() != flat_g.numel() or flat_p.numel() < n:
+                raise ValueError(f"FlatBuffers: the storage holds {flat_p.numel()} / {flat_g.numel()} elements, the "
+                                 f"parameters need {n}")
+            self.numel, self.flat_p, self.flat_g = flat_p.numel(), flat_p, flat_g
         for p, o in zip(self.params, self.offsets):
             v = self.flat_p[o:o + p.numel()].view(p.shape)
             v.copy_(p.data)
             p.data = v
             p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
+
+    @classmethod
+    def joined(cls, parts: List["FlatBuffers"], starts: List[int], flat_p: torch.Tensor,
+               flat_g: torch.Tensor) -> "FlatBuffers":
+        """The arena that the given FlatBuffers were built over (parts[k] occupies flat_p[starts[k]:][:numel]) seen as
+        one FlatBuffers: every part's parameters in arena order with arena offsets.  Re-homes nothing; it is what one
+        GradSync and one zero_grad over the whole arena need."""
+        self = cls.__new__(cls)
+        self.params = [p for f in parts for p in f.params]
+        self.offsets = [s + o for f, s in zip(parts, starts) for o in f.offsets]
+        self.numel, self.flat_p, self.flat_g = flat_p.numel(), flat_p, flat_g
+        return self
 
     def zero_grad(self):
         self.flat_g.zero_()

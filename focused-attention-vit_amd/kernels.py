@@ -1170,6 +1170,73 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None
                "favit_adamw_clip")
 
 
+def _adamw_limits():
+    """(FAVIT_ADAMW_MAX_SEGMENTS, FAVIT_ADAMW_SEG_ALIGN) as the loaded library reports them."""
+    got = (int(_abi.lib().favit_adamw_multi_max_segments()), int(_abi.lib().favit_adamw_multi_align()))
+    if got != (_abi.ADAMW_MAX_SEGMENTS, _abi.ADAMW_SEG_ALIGN):
+        raise _abi.FavitLibraryError("libfavit.so and _abi.AdamwMulti disagree on the segment table's size")
+    return got
+
+
+def __getattr__(name):
+    """ADAMW_MAX_SEGMENTS / ADAMW_SEG_ALIGN: read from the library at first use, so that importing this module still
+    does not need the library."""
+    if name in ("ADAMW_MAX_SEGMENTS", "ADAMW_SEG_ALIGN"):
+        return _adamw_limits()[name == "ADAMW_SEG_ALIGN"]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def adamw_multi(p, g, m, v, ends, lrs, wds, beta1, beta2, eps, step, grad_scale=1.0, p_lp=None, coef=None,
+                skip_nonfinite=False, ema=None, ema_decay=0.0):
+    """adamw() over ONE arena cut into len(ends) segments, in one launch (favit_adamw_multi): segment s covers
+    [ends[s-1], ends[s]) (ends exclusive, strictly ascending multiples of ADAMW_SEG_ALIGN, the last one p.numel()) and
+    is updated with lrs[s] and wds[s]; everything else is shared.  Per element the bits are adamw()'s on the segment's
+    slice.  The table is a by-value argument of the launch: plain Python numbers, read at every call.  coef,
+    skip_nonfinite, ema, ema_decay: as in adamw().  ValueError for a table the library would refuse."""
+    ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN = _adamw_limits()
+    ends, lrs, wds = [int(e) for e in ends], [float(x) for x in lrs], [float(x) for x in wds]
+    require_gpu(p, g, m, v, p_lp, ema, coef)
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+            raise TypeError(f"adamw_multi: {name} must be a contiguous fp32 tensor of p's length")
+    n = p.numel()
+    if p_lp is not None and (p_lp.dtype != torch.bfloat16 or p_lp.numel() != n or not p_lp.is_contiguous()):
+        raise TypeError("adamw_multi: p_lp must be a contiguous bf16 tensor of p's length")
+    if ema is not None:
+        if ema.dtype != torch.float32 or ema.numel() != n or not ema.is_contiguous():
+            raise TypeError("adamw_multi: ema must be a contiguous fp32 tensor of p's length")
+        if not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError(f"adamw_multi: ema_decay must be in [0, 1], got {ema_decay}")
+    if coef is None:
+        if skip_nonfinite:
+            raise ValueError("adamw_multi: skip_nonfinite needs the device coefficient of grad_norm (coef)")
+    elif coef.dtype != torch.float32 or coef.numel() != 1:
+        raise TypeError("adamw_multi: coef must be one fp32 on the device")
+    if not 1 <= len(ends) <= ADAMW_MAX_SEGMENTS:
+        raise ValueError(f"adamw_multi: 1..{ADAMW_MAX_SEGMENTS} segments per launch, got {len(ends)}")
+    if len(lrs) != len(ends) or len(wds) != len(ends):
+        raise ValueError(f"adamw_multi: {len(ends)} ends, {len(lrs)} learning rates and {len(wds)} weight decays")
+    prev = 0
+    for s, e in enumerate(ends):
+        if e <= prev or e % ADAMW_SEG_ALIGN:
+            raise ValueError(f"adamw_multi: end {e} of segment {s} must be a multiple of {ADAMW_SEG_ALIGN} above the "
+                             f"previous end {prev}")
+        prev = e
+    if prev != n:
+        raise ValueError(f"adamw_multi: the last end is {prev}, the arena has {n} elements")
+    for name, t, a in (("p", p, 16), ("g", g, 16), ("m", m, 16), ("v", v, 16), ("ema", ema, 16), ("p_lp", p_lp, 8)):
+        if t is not None and t.data_ptr() % a:
+            raise ValueError(f"adamw_multi: {name} must be {a}-byte aligned")
+    d = _abi.AdamwMulti()
+    d.p, d.g, d.m, d.v, d.p_bf16, d.ema, d.coef = _p(p), _p(g), _p(m), _p(v), _p(p_lp), _p(ema), _p(coef)
+    d.n, d.count, d.skip_nonfinite = n, len(ends), int(bool(skip_nonfinite))
+    for s in range(len(ends)):
+        d.end[s], d.lr[s], d.weight_decay[s] = ends[s], lrs[s], wds[s]
+    d.beta1, d.beta2, d.eps, d.bias_c1, d.bias_c2 = beta1, beta2, eps, 1.0 - beta1 ** step, 1.0 - beta2 ** step
+    d.grad_scale, d.ema_decay = grad_scale, float(ema_decay)
+    _abi.check(_abi.lib().favit_adamw_multi(C.byref(d), _st()), "favit_adamw_multi")
+
+
 def swap_params(a, b, a_lp=None):
     """Exchange the contents of two flat fp32 tensors in place and, with a_lp, rewrite the bf16 mirror of `a` from
     its new contents, in one pass (favit_swap_params).  No address changes."""

@@ -44,9 +44,23 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: f
 
 
 def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = None,
-                 latent_lr_mult: float = 5.0) -> List[Dict]:
+                 latent_lr_mult: float = 5.0, layer_decay: Optional[float] = None, no_weight_decay=None) -> List[Dict]:
     """The reference's name-based groups (experiments/mhla_pretrained.py:320-327): every
-    trainable parameter whose name contains 'latent_proj' trains at 5x lr, 'head' at head_lr."""
+    trainable parameter whose name contains 'latent_proj' trains at 5x lr, 'head' at head_lr.
+
+    The two fine-tuning refinements (both off by default; with both off the list is the three groups above):
+    no_weight_decay="auto": parameters with ndim <= 1 (biases, LayerNorm weights) and those whose last name component
+        is cls_token or pos_embed go into groups carrying "weight_decay": 0.0; the other groups carry no such key (the
+        optimizer's default applies).  An iterable of name substrings exempts by name instead.
+    layer_decay=d, 0 < d <= 1: with depth = 1 + the largest i of the names blocks.i.*, a parameter of layer id k trains
+        at its category rate (head_lr / lr * latent_lr_mult / lr, as above) times d ** (depth + 1 - k), where
+        blocks.i.* has id i + 1, names containing 'head' and the final norm.* have id depth + 1 and everything in
+        front of the blocks (cls_token, pos_embed, patch_embed.*, the SPPP front end) id 0.
+    With either, parameters of equal (rate, weight decay) share a group, no two groups have the same pair, and the
+    groups come in descending layer id -- the order in which backward completes their gradients, so that
+    FusedAdamW(fuse_groups=True) fills its arena (and its all-reduce buckets) in that order."""
+    if layer_decay is not None or no_weight_decay is not None:
+        return _recipe_groups(model, lr, head_lr, latent_lr_mult, layer_decay, no_weight_decay)
     base, lat, head = [], [], []
     for n, p in model.named_parameters():
         if not p.requires_grad:
@@ -63,6 +77,55 @@ def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = N
     if head:
         out.append({"params": head, "lr": head_lr if head_lr is not None else lr})
     return [g for g in out if g["params"]]
+
+
+def _recipe_groups(model, lr, head_lr, latent_lr_mult, layer_decay, no_weight_decay) -> List[Dict]:
+    """param_groups with layer_decay and / or no_weight_decay (see there)."""
+    import re
+    if layer_decay is not None and not 0.0 < float(layer_decay) <= 1.0:
+        raise ValueError(f"param_groups: layer_decay must be in (0, 1], got {layer_decay}")
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    block_of = {n: int(mt.group(1)) for n, _ in model.named_parameters()
+                for mt in [re.match(r"^blocks\.(\d+)\.", n)] if mt}
+    if layer_decay is not None and not block_of:
+        raise ValueError("param_groups: layer_decay needs parameters named blocks.<i>.*, the model has none")
+    depth = 1 + max(block_of.values()) if block_of else 0
+    if no_weight_decay is None:
+        exempt = lambda n, p: False
+    elif isinstance(no_weight_decay, str):
+        if no_weight_decay != "auto":
+            raise ValueError(f"param_groups: no_weight_decay is 'auto' or an iterable of name substrings, got "
+                             f"{no_weight_decay!r}")
+        exempt = lambda n, p: p.ndim <= 1 or n.rsplit(".", 1)[-1] in ("cls_token", "pos_embed")
+    else:
+        subs = tuple(no_weight_decay)
+        exempt = lambda n, p: any(s in n for s in subs)
+    groups: Dict = {}
+    for n, p in named:
+        if n in block_of:
+            k = block_of[n] + 1
+        elif "head" in n or n.startswith("norm."):
+            k = depth + 1
+        else:
+            k = 0
+        if "head" in n:
+            rate = head_lr if head_lr is not None else lr
+        elif "latent_proj" in n:
+            rate = lr * latent_lr_mult
+        else:
+            rate = lr
+        if layer_decay is not None:
+            rate = rate * layer_decay ** (depth + 1 - k)
+        key = (rate, 0.0 if exempt(n, p) else None)
+        g = groups.setdefault(key, {"params": [], "layer": k})
+        g["params"].append(p)
+        g["layer"] = max(g["layer"], k)
+    out = []
+    for (rate, wd), g in sorted(groups.items(), key=lambda kv: -kv[1]["layer"]):      # (stable: ties keep name order)
+        out.append({"params": g["params"], "lr": rate})
+        if wd is not None:
+            out[-1]["weight_decay"] = wd
+    return out
 
 
 def ema_decay_at(decay: float, n: int, warmup: bool = False) -> float:
@@ -101,7 +164,8 @@ class FusedAdamW:
     skip): the next applied update uses bias-correction factors one step further on, which after the first few
     steps is a difference far below the update's own rounding.
     Read-outs (None when both options are off): `grad_norm`, a 0-dim fp32 device view of the last step's pre-clip
-    norm, and `skipped_steps`, a 0-dim int32 device view.  Both options need at most 16 parameter groups.
+    norm, and `skipped_steps`, a 0-dim int32 device view.  Both options need at most 16 parameter groups (per-group
+    layout; fuse_groups=True has no such limit).
 
     ema_decay (in [0, 1), None = off): every group keeps `g["ema"]`, an fp32 flat buffer laid out like flat_p and
     initialised as a copy of it, and the group's AdamW launch itself moves it towards the parameters it has just
@@ -113,11 +177,21 @@ class FusedAdamW:
     parallelism every rank's average is bitwise the same (same p, same decay).
 
     state_dict(model) / load_state_dict(state, model): m, v and the average per parameter, keyed by the model's
-    state_dict names (independent of the flat layout), the hyper-parameters per group and the counters."""
+    state_dict names (independent of the flat layout), the hyper-parameters per group and the counters.
+
+    fuse_groups=True (off by default; off is the layout and the launches above): all groups live in ONE arena, each in
+    a range that starts and ends on a 256-element boundary, in the order given; inside a range the tensors keep the
+    4-element alignment and the reverse registration order.  step() is then one favit_adamw_multi launch per 64 groups
+    with a learning rate and weight decay per range (per element the bits of the per-group launch), with the guard one
+    norm over the arena in front (any number of groups); zero_grad() is one memset, ema_weights() one exchange, and one
+    bf16 mirror and ONE GradSync (groups[0]["sync"] / ["mirror"], None in the others; buckets may cross groups)
+    cover the arena.  `groups` keeps its keys, every buffer a view of the group's range, so schedules, checkpoints
+    (interchangeable with a per-group optimizer of the same grouping), Health.report and GraphedStep work unchanged.
+    betas and eps are shared by the launch: groups that differ in them raise ValueError."""
 
     def __init__(self, groups, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, bucket_mb=None,
                  distributed=None, wire_dtype=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None,
-                 ema_warmup=False):
+                 ema_warmup=False, fuse_groups=False):
         if isinstance(groups, torch.nn.Module):
             groups = [{"params": list(groups.parameters())}]
         elif groups and not isinstance(groups[0], dict):
@@ -133,11 +207,15 @@ class FusedAdamW:
         self.ema_warmup = bool(ema_warmup)
         self.ema_updates = 0
         self._ema_swapped = False
-        if self._guard and len(groups) > K.GRAD_NORM_MAX_BUFS:
+        self.fuse_groups = bool(fuse_groups)
+        if self._guard and not self.fuse_groups and len(groups) > K.GRAD_NORM_MAX_BUFS:
             raise ValueError(f"FusedAdamW: max_grad_norm / skip_nonfinite take at most {K.GRAD_NORM_MAX_BUFS} parameter "
                              f"groups, got {len(groups)}")
         self.groups = []
         dist_on = torch.distributed.is_initialized() if distributed is None else distributed
+        if self.fuse_groups:
+            self._init_fused(groups, lr, betas, eps, weight_decay, bucket_mb, wire_dtype, dist_on)
+            groups = []                                # (built above; the per-group loop has nothing left to do)
         for g in groups:
             flat = FlatBuffers(g["params"])
             self.groups.append({
@@ -174,6 +252,60 @@ class FusedAdamW:
         if syncs:
             F.set_grad_ready_hook(lambda p: [s.grad_ready(p) for s in syncs])
 
+    def _init_fused(self, groups, lr, betas, eps, weight_decay, bucket_mb, wire_dtype, dist_on):
+        """fuse_groups=True: every group is a range of ONE arena (parameters, gradients, m, v, bf16 mirror, average),
+        starting and ending on a K.ADAMW_SEG_ALIGN boundary; the padding is zero and stays zero.  self.groups keeps
+        its shape -- every buffer of a group is a view of its range -- so schedules, checkpoints and reports do not
+        know the difference; the arena-wide objects (one GradSync, one mirror) sit in groups[0]."""
+        align = K.ADAMW_SEG_ALIGN
+        if not groups:
+            raise ValueError("FusedAdamW: fuse_groups needs at least one parameter group")
+        hyper = [(tuple(g.get("betas", betas)), g.get("eps", eps)) for g in groups]
+        if any(h != hyper[0] for h in hyper):
+            raise ValueError("FusedAdamW: fuse_groups shares betas and eps among all groups (one launch), got "
+                             f"{sorted(set(hyper))}")
+        starts, n = [], 0
+        for g in groups:
+            size = FlatBuffers.size_of(g["params"])
+            if not size:
+                raise ValueError("no trainable parameters")
+            starts.append(n)
+            n += (size + align - 1) // align * align
+        ends = starts[1:] + [n]
+        dev = next(p for p in groups[0]["params"] if p.requires_grad).device
+        if self.ema_decay is not None and dev.type != "cuda":
+            raise RuntimeError("FusedAdamW: ema_decay runs in HIP kernels; the parameters are on the CPU (there "
+                               "is no CPU fallback)")
+        new = lambda: torch.zeros(n, dtype=torch.float32, device=dev)
+        a = {"p": new(), "g": new(), "m": new(), "v": new(), "lp": None, "ema": None}
+        if dev.type == "cuda":
+            a["lp"] = torch.empty(n, dtype=torch.bfloat16, device=dev)
+        for g, s, e in zip(groups, starts, ends):
+            flat = FlatBuffers(g["params"], a["p"][s:e], a["g"][s:e])
+            self.groups.append({
+                "flat": flat, "lr": g.get("lr", lr), "betas": g.get("betas", betas), "eps": g.get("eps", eps),
+                "weight_decay": g.get("weight_decay", weight_decay), "m": a["m"][s:e], "v": a["v"][s:e],
+                "lp": None if a["lp"] is None else a["lp"][s:e], "sync": None, "mirror": None,
+            })
+        whole = FlatBuffers.joined([g["flat"] for g in self.groups], starts, a["p"], a["g"])
+        if dist_on:
+            self.groups[0]["sync"] = GradSync(whole, bucket_mb, wire_dtype=wire_dtype)   # buckets may cross groups
+        if a["lp"] is not None:
+            K.cast(a["p"], torch.bfloat16, out=a["lp"])
+            self.groups[0]["mirror"] = F.register_lp_mirror(a["p"], a["lp"], whole.params)
+        if self.ema_decay is not None:
+            a["ema"] = a["p"].clone()
+            for g, s, e in zip(self.groups, starts, ends):
+                g["ema"] = a["ema"][s:e]
+        self._arena, self._arena_flat, self._starts, self._ends = a, whole, starts, ends
+        # one launch per K.ADAMW_MAX_SEGMENTS groups: the views every launch takes, made once (step() allocates nothing)
+        self._launches = []
+        for i in range(0, len(groups), K.ADAMW_MAX_SEGMENTS):
+            j = min(len(groups), i + K.ADAMW_MAX_SEGMENTS)
+            lo, hi = starts[i], ends[j - 1]
+            self._launches.append((i, j, [e - lo for e in ends[i:j]],
+                                   {k: (None if t is None else t[lo:hi]) for k, t in a.items()}))
+
     def no_sync(self):
         """Gradient accumulation under data parallelism: ``with opt.no_sync(): loss.backward()`` for every
         micro-batch but the last (dp.GradSync.no_sync)."""
@@ -185,6 +317,12 @@ class FusedAdamW:
         return stack
 
     def zero_grad(self):
+        if self.fuse_groups:
+            sync = self.groups[0]["sync"]
+            if sync is not None and (sync._handles or any(sync._launched)):
+                sync.abort()                           # (as below)
+            self._arena_flat.zero_grad()               # one memset for every group
+            return
         for g in self.groups:
             if g["sync"] is not None and (g["sync"]._handles or any(g["sync"]._launched)):
                 # the previous backward did not reach step() (it raised, or the caller skipped the step): its
@@ -212,6 +350,8 @@ class FusedAdamW:
             d = ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)
             self.ema_updates += 1
             ema_kw = [{"ema": g["ema"], "ema_decay": d} for g in self.groups]
+        if self.fuse_groups:
+            return self._step_fused(ema_kw[0].get("ema_decay", 0.0))
         if self._guard:
             for g in self.groups:                      # the norm is that of the COMPLETE all-reduced gradient
                 if g["sync"] is not None:
@@ -236,18 +376,41 @@ class FusedAdamW:
         # the AdamW kernel rewrote the bf16 mirrors itself: they stay valid across the epoch bump
         F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
 
+    def _step_fused(self, ema_decay):
+        """step() over the arena: one all-reduce stream, one norm over one buffer (no limit on the number of groups),
+        one favit_adamw_multi launch per K.ADAMW_MAX_SEGMENTS groups with the groups' CURRENT lr / weight_decay."""
+        g0 = self.groups[0]
+        if any(tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"] for g in self.groups):
+            raise ValueError("FusedAdamW: fuse_groups shares betas and eps among all groups (one launch)")
+        if g0["sync"] is not None:
+            g0["sync"].finish(average=False)
+        coef = None
+        if self._guard:
+            K.grad_norm([self._arena["g"]], scale=1.0 / self.world, max_norm=self.max_grad_norm or 0.0,
+                        out=self._norm_out, skipped=self._skipped, ws=self._norm_ws)
+            coef = self._norm_out[1:2]
+        for i, j, ends, a in self._launches:
+            K.adamw_multi(a["p"], a["g"], a["m"], a["v"], ends, [g["lr"] for g in self.groups[i:j]],
+                          [g["weight_decay"] for g in self.groups[i:j]], g0["betas"][0], g0["betas"][1], g0["eps"],
+                          self.steps, grad_scale=1.0 / self.world, p_lp=a["lp"], coef=coef,
+                          skip_nonfinite=self.skip_nonfinite, ema=a["ema"], ema_decay=ema_decay)
+        F.bump_weight_epoch([g0["mirror"]] if g0["mirror"] is not None else [])
+
     # ---- averaged weights ----
     def _swap_ema(self):
-        for g in self.groups:
-            K.swap_params(g["flat"].flat_p, g["ema"], g["lp"])
+        if self.fuse_groups:
+            K.swap_params(self._arena["p"], self._arena["ema"], self._arena["lp"])     # one exchange for every group
+        else:
+            for g in self.groups:
+                K.swap_params(g["flat"].flat_p, g["ema"], g["lp"])
         # as after step(): the parameters changed through raw pointers, the mirrors were rewritten with them
         F.bump_weight_epoch([g["mirror"] for g in self.groups if g["mirror"] is not None])
 
     @contextlib.contextmanager
     def ema_weights(self):
         """``with opt.ema_weights(): evaluate(model)``: inside, the trainable parameters (and their bf16 mirrors) hold
-        the average and `g["ema"]` holds the training weights; one favit_swap_params launch per group on entry and
-        on exit (also when the body raises), no address changes -- a captured GraphedStep stays valid.  Frozen
+        the average and `g["ema"]` holds the training weights; one favit_swap_params launch per group (one in all with
+        fuse_groups) on entry and on exit (also when the body raises), no address changes -- a captured GraphedStep stays valid.  Frozen
         parameters are untouched.  Nesting and step() inside the context raise RuntimeError."""
         if self.ema_decay is None:
             raise RuntimeError("FusedAdamW.ema_weights(): the optimizer keeps no average (ema_decay=None)")

@@ -634,6 +634,38 @@ int favit_adamw_clip_ema(float* p, const float* g, float* m, float* v, void* p_b
 int favit_swap_params(float* a, float* b, void* a_bf16, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Segmented AdamW (additive in ABI 8): ONE launch over one arena that holds every parameter group, with a learning
+ * rate and a weight decay per segment.  For every element of segment s, p, m, v, p_bf16 and ema get exactly the bits
+ * the single-group entry point of the same form (plain / _clip / _ema / _clip_ema, chosen by coef and ema being
+ * non-NULL) gives for the same inputs with lr[s] and weight_decay[s].  The table travels by value in the kernel
+ * arguments: no device table, no copy per step, nothing that must outlive the call; changed rates are picked up by
+ * the next call.  Segment ends are multiples of FAVIT_ADAMW_SEG_ALIGN elements (one wave x 16 bytes per lane), so a
+ * wave never straddles two segments; padding elements between groups are zero in p, g, m, v (and ema) and stay zero.
+ * Refused with FAVIT_ERR_INVALID before anything is launched: count outside 1..FAVIT_ADAMW_MAX_SEGMENTS, an end that
+ * is not a multiple of the alignment or not strictly ascending, end[count-1] != n, a NULL p / g / m / v, p / g / m / v
+ * / ema not 16-byte aligned, p_bf16 not 8-byte aligned, skip_nonfinite without coef, ema with ema_decay outside [0, 1].
+ * Health word: as the single-group launches, and the whole arena counts as ONE AdamW launch.
+ * ---------------------------------------------------------------------------------- */
+#define FAVIT_ADAMW_MAX_SEGMENTS 64
+#define FAVIT_ADAMW_SEG_ALIGN    256   /* elements */
+typedef struct favit_adamw_multi {
+  float* p; const float* g; float* m; float* v;   /* [n] fp32 each, 16-byte aligned */
+  void* p_bf16;            /* [n] bf16 mirror of p, 8-byte aligned, or NULL */
+  float* ema;              /* [n] fp32 average, 16-byte aligned, or NULL */
+  int64_t n;               /* arena length, a multiple of FAVIT_ADAMW_SEG_ALIGN */
+  int32_t count;           /* 1..FAVIT_ADAMW_MAX_SEGMENTS */
+  int32_t skip_nonfinite;  /* with coef: a non-finite coef[0] writes nothing but the health word */
+  int64_t end[FAVIT_ADAMW_MAX_SEGMENTS];  /* exclusive ends, strictly ascending, multiples of the alignment, end[count-1] == n */
+  float lr[FAVIT_ADAMW_MAX_SEGMENTS];
+  float weight_decay[FAVIT_ADAMW_MAX_SEGMENTS];
+  float beta1, beta2, eps, bias_c1, bias_c2, grad_scale, ema_decay;
+  const float* coef;       /* device scalar of favit_grad_norm (out + 1), or NULL for the unclipped form */
+} favit_adamw_multi_t;
+int favit_adamw_multi(const favit_adamw_multi_t* d, void* stream);
+int favit_adamw_multi_max_segments(void);
+int favit_adamw_multi_align(void);
+
+/* ------------------------------------------------------------------------------------
  * Batch mixing (additive in ABI 8): Mixup / CutMix of a batch with its own flip (timm's Mixup), and the loss of the
  * mixed targets.  Row b is paired with row p = B-1-b; with B odd the middle row is its own partner and never changes.
  * ---------------------------------------------------------------------------------- */

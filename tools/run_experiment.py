@@ -189,6 +189,14 @@ def parse_args(argv=None):
                          "file PATH.ema with the averaged weights (the plain weights without --ema_decay)")
     ap.add_argument("--checkpoint_every", type=int, default=1, metavar="N", help="--checkpoint: every N epochs")
     ap.add_argument("--resume", action="store_true", help="--checkpoint: continue from PATH if it exists")
+    ap.add_argument("--layer_decay", type=float, default=None, metavar="F",
+                    help="layer-wise learning-rate decay: block i trains at F ** (depth - i) of the top rate "
+                         "(train.param_groups(layer_decay=F)); builds the optimizer with fuse_groups=True")
+    ap.add_argument("--no_wd_norm_bias", action="store_true",
+                    help="no weight decay on biases, LayerNorm weights, cls_token and pos_embed "
+                         "(train.param_groups(no_weight_decay='auto')); builds the optimizer with fuse_groups=True")
+    ap.add_argument("--fuse_groups", action="store_true",
+                    help="one arena and one AdamW launch for all parameter groups (train.FusedAdamW(fuse_groups=True))")
     ap.add_argument("--bucket_tokens", action="store_true",
                     help="sppp_mhla: run batches that mix images with num_superpixels and num_superpixels - 1 tokens group by "
                          "group (models.sppp.TokenBucketed; the reference -- and this tool without the flag -- fails on "
@@ -238,10 +246,17 @@ def main(argv=None):
               f"{sum(p.numel() for p in model.parameters()):,}")
     model = model.cuda()
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
-    opt = pkg.train.FusedAdamW(pkg.train.param_groups(model, lr=a.learning_rate, head_lr=a.head_learning_rate),
+    group_kw, opt_kw = {}, {}          # (none of the three flags: exactly the groups and the optimizer of before)
+    if a.layer_decay is not None:
+        group_kw["layer_decay"] = a.layer_decay
+    if a.no_wd_norm_bias:
+        group_kw["no_weight_decay"] = "auto"
+    if group_kw or a.fuse_groups:
+        opt_kw["fuse_groups"] = True
+    opt = pkg.train.FusedAdamW(pkg.train.param_groups(model, lr=a.learning_rate, head_lr=a.head_learning_rate, **group_kw),
                                lr=a.learning_rate, weight_decay=a.weight_decay, distributed=False,
                                max_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay,
-                               ema_warmup=a.ema_warmup)
+                               ema_warmup=a.ema_warmup, **opt_kw)
     if a.eval_ema and a.ema_decay is None:
         raise SystemExit("--eval_ema needs --ema_decay")
     if (a.resume or a.checkpoint_every != 1) and a.checkpoint is None:
