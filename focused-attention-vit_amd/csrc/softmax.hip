@@ -27,13 +27,16 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
     m = fmaxf(m, v);
   }
   m = wave_max(m);
+  // every key masked (include/favit.h): the row stores zeros -- with m = -inf, v - m below would be NaN
+  const bool dead = m == -INFINITY;
+  if (dead) m = 0.f;
   float l = 0.f;
   for (int k = lane; k < Lk; k += 64) {
     const float v = (mrow && mrow[k] == 0) ? -INFINITY : s[k];
     l += __expf(v - m);
   }
   l = wave_sum(l);
-  const float inv = 1.0f / l;
+  const float inv = dead ? 0.f : 1.0f / l;
   for (int k = lane; k < Lk; k += 64) {
     const float v = (mrow && mrow[k] == 0) ? -INFINITY : s[k];
     const float p = __expf(v - m) * inv;

@@ -919,7 +919,16 @@ class CrossChain:
         dkn = torch.empty((Mk, D), dtype=torch.float32, device=qn.device)
         K.gemm(dk, wk_c, dkn, Mk, D, D, D, D, D, b_kmajor=False)
         K.gemm(dv, wv_c, dkn, Mk, D, D, D, D, D, b_kmajor=False, accumulate=True)
-        dwk, dbk = lin_bwd_w(dk, kn, Mk, D, D, wp=wk, bp=bk)
+        # (the key bias adds q.bk to every score of a query row, which softmax removes: every row of dS sums to 0 under
+        # any mask and dropout, so dbk is exactly 0.  The column sum of the stored dk would leave its rounding there --
+        # ~1e-3 in bf16 -- which an optimizer that normalises gradients turns into a random walk of the bias.)
+        dwk, _ = lin_bwd_w(dk, kn, Mk, D, D, want_bias=False, wp=wk)
+        dbk = None
+        if bk.requires_grad:
+            if _gt(bk) is not None:
+                _ready(bk)                   # nothing to add to the gradient buffer
+            else:
+                dbk = _zero_vec(D, dk.device)
         dwv, dbv = lin_bwd_w(dv, kn, Mk, D, D, wp=wv, bp=bv)
         return dqn, dkn, [dwq, dbq, dwk, dbk, dwv, dbv, dwo, dbo]
 

@@ -330,6 +330,11 @@ int favit_mhla_attn_bwd_lse(const void* qkv, const void* dout, const void* o, co
  * mask (uint8, 0 = -inf) is addressed mask[(z / H) * m_sb + q * m_sq + k].
  * P (dtype p_dtype) gets softmax(S); if dropout_p>0, Pd gets the dropped+rescaled P.
  * Backward: dS = P * (dPd*keep/(1-p) - sum_k(...)) in ds_dtype.
+ * dropout: inverted, counter-based on (seed, (z*Lq + q)*Lk + k) -- with z = b*H + h the draw of favit_sdpa_fwd.
+ * A row whose keys are ALL masked (PyTorch's softmax gives NaN there) follows the contract of favit_sdpa_fwd below:
+ * fwd stores P = 0 (and Pd = 0) for the whole row, so the P.V GEMM gives o = 0 for it; bwd then gives dS = 0 for it
+ * (dS = P * (...) with P = 0 and finite dPd), so dq = 0 and the row adds nothing to dk or dv.  No other row is
+ * affected and nothing non-finite is written.  A masked entry of a live row has P = 0 exactly.
  * ---------------------------------------------------------------------------------- */
 int favit_softmax_fwd(const float* S, void* P, void* Pd, int p_dtype, const uint8_t* mask, int64_t m_sb,
                       int64_t m_sq, int32_t H, int64_t Z, int32_t Lq, int32_t Lk, float dropout_p, uint64_t seed,

@@ -122,6 +122,21 @@ def sdpa_ref(q, k, v, dout, scale, mask, keep, p):
     return o.detach(), torch.logsumexp(s.detach(), -1), qr.grad, kr.grad, vr.grad
 
 
+def cross_attention_ref(q_in, kv_in, sd, H, mask=None, p=""):
+    """O.cross_attention (H = 1: one head of width D, scores / D**0.5) and O.multihead_cross_attention restated around
+    _sdpa_probs, so that a query row with every key masked has P = 0 where the oracle's torch.softmax gives NaN: its
+    output row is out_proj.bias and it sends no gradient into q, k or v.  q_in [B, Lq, D], kv_in [B, Lk, D], mask
+    [B, Lq, Lk] (0 = masked) or None; any float dtype (tests/test_head_widths_host.py ties it to the oracle in float64)."""
+    B, Lq, D = q_in.shape
+    Lk, hd = kv_in.shape[1], D // H
+    q = O.linear(q_in, sd[f"{p}q_proj.weight"], sd[f"{p}q_proj.bias"]).reshape(B, Lq, H, hd).permute(0, 2, 1, 3)
+    k = O.linear(kv_in, sd[f"{p}k_proj.weight"], sd[f"{p}k_proj.bias"]).reshape(B, Lk, H, hd).permute(0, 2, 1, 3)
+    v = O.linear(kv_in, sd[f"{p}v_proj.weight"], sd[f"{p}v_proj.bias"]).reshape(B, Lk, H, hd).permute(0, 2, 1, 3)
+    _, P = _sdpa_probs(q, k, 1.0 / hd ** 0.5, None if mask is None else (mask != 0)[:, None])
+    o = (P @ v).permute(0, 2, 1, 3).reshape(B, Lq, D)
+    return O.linear(o, sd[f"{p}out_proj.weight"], sd[f"{p}out_proj.bias"])
+
+
 def sdpa_grad_scale(q, k, v, dout, scale, mask, keep, p):
     """The size of the terms whose sum is dq and dk: dS = P (dP - delta) with |dP| + |delta| in place of the
     difference and |k|, |q| in place of k, q.  Where a gradient is identically zero by cancellation (one key:
