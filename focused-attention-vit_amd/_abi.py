@@ -143,6 +143,8 @@ _SIGS = {
     "favit_mhla_block_mlp_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
     "favit_mhla_block_attn_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
     "favit_dropout": ([vp, vp, C.c_int, i64, f32, u64, vp], C.c_int),
+    "favit_drop_path_add": ([vp, vp, C.c_int, vp, i32, i32, i32, f32, u64, vp], C.c_int),
+    "favit_drop_path_bwd": ([vp, vp, C.c_int, i32, i32, i32, f32, u64, f32, u64, vp], C.c_int),
     "favit_sppp_map_patches": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
     "favit_sppp_pool_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
     "favit_sppp_pool_bwd": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),

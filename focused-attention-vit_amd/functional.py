@@ -1126,10 +1126,13 @@ class PrologueOp:
 
 class BlockSpec:
     """Static description of one pre-LN transformer block (models/vit.py:165-179,
-    models/vit_mhla.py:77-109, models/mhla.py:205-222)."""
+    models/vit_mhla.py:77-109, models/mhla.py:205-222).  drop_path: stochastic depth rate of both residual branches
+    (as timm's two DropPath modules of a block; not in the reference), active in training mode only -- see EncoderOp."""
 
-    def __init__(self, attn, mlp):
-        self.attn, self.mlp = attn, mlp
+    def __init__(self, attn, mlp, drop_path=0.0):
+        if not 0.0 <= float(drop_path) < 1.0:
+            raise ValueError("drop_path must lie in [0, 1)")
+        self.attn, self.mlp, self.drop_path = attn, mlp, float(drop_path)
         self.names = (("norm1.weight", "norm1.bias") + tuple("attn." + n for n in attn.names) +
                       ("norm2.weight", "norm2.bias") + tuple("mlp." + n for n in mlp.names))
         self.n = len(self.names)
@@ -1234,14 +1237,17 @@ class _Tape:
     (behind cut / mcut); ln1 / ln2: (gamma, beta); sa / sm: what the two chains saved; pa / pm: their parameters.
     cut = (n_in, head, tail): the stream was cut from n_in rows to head + tail in front of the block, mcut: the same
     between its halves, None: no cut there.  rows: token rows (batch x rows per image) the tape holds operands for,
-    both halves together (the ratio of two blocks scales the bytes their weight-gradient operands keep alive)."""
-    __slots__ = ("x", "mu1", "rs1", "ln1", "sa", "x1", "mu2", "rs2", "ln2", "sm", "pa", "pm", "cut", "mcut", "rows")
+    both halves together (the ratio of two blocks scales the bytes their weight-gradient operands keep alive).
+    dpa / dpm: (rate, seed) of the drop-path draw of the attention / MLP half, None where the half was not dropped."""
+    __slots__ = ("x", "mu1", "rs1", "ln1", "sa", "x1", "mu2", "rs2", "ln2", "sm", "pa", "pm", "cut", "mcut", "rows",
+                 "dpa", "dpm")
     native = False
 
     def __init__(self, *fields):
         for k, v in zip(self.__slots__, fields):
             setattr(self, k, v)
         self.rows = self.x.shape[0] + self.x1.shape[0]
+        self.dpa = self.dpm = None
 
 
 class _NativeTape:
@@ -1254,6 +1260,7 @@ class _NativeTape:
     __slots__ = ("plan", "buf", "x", "ln1", "ln2", "pa", "pm", "weff", "wc", "cut", "mcut", "rows", "mlp_in_tape",
                  "mu1", "rs1", "sa", "x1", "mu2", "rs2", "sm", "_bf", "_f32")
     native = True
+    dpa = dpm = None              # (a block with an active drop-path rate never runs the native chain)
 
     def __init__(self, plan, buf, x, ln1, ln2, pa, pm, weff, wc, cut):
         self.plan, self.buf, self.x, self.ln1, self.ln2, self.pa, self.pm = plan, buf, x, ln1, ln2, pa, pm
@@ -1303,7 +1310,20 @@ class EncoderOp:
     (favit_rows_cut_bwd).
     mlp_cuts (mlp_narrow_plan): per block the (head, tail) rows its MLP half runs on, or None.  The stream is then cut
     inside the block, after proj + residual, and the next block finds its rows in place: the cut in front of it moves
-    up into this block."""
+    up into this block.
+
+    Stochastic depth.  A half is "dropped" iff `training` and its block's BlockSpec.drop_path
+    is > 0: x += keep(b) / (1 - p) * branch(LN(x)) per sample b.  Its chain runs with residual=None (the proj / fc2
+    GEMM writes the fp32 branch, output dropout still in its epilogue) and K.drop_path_add makes the sum on the half's
+    own row count; backward scales and masks the branch gradient in K.drop_path_bwd (which also carries the branch's
+    output-dropout mask, so the chain runs premasked) while the LayerNorm backward keeps adding the unscaled stream
+    gradient.  The draw is indexed by the sample alone: pruning (cuts / mlp_cuts) does not change it.
+    SEED ORDER (part of the interface; tests rebuild the masks from it): one _seed() per dropped half, drawn right
+    AFTER the dropout seeds of that half's own chain (attention: p_attn, then p_proj; MLP: fc1, then fc2, each only
+    where its rate is > 0); within a block the attention half first, then the MLP half; blocks in order.  A half
+    with rate 0, and every half in eval mode, draws nothing and runs exactly the code it ran before.
+    fp8 compute mode with an active rate raises NotImplementedError (the q8 hand-offs between the LayerNorm backward
+    and the GEMMs are not covered)."""
 
     def __init__(self, blocks: List[BlockSpec], mask=None, training=False, cuts=None, mlp_cuts=None):
         self.blocks, self.mask, self.training = blocks, mask, training
@@ -1354,10 +1374,18 @@ class EncoderOp:
             mc = self.mlp_cuts[bi] if self.mlp_cuts is not None else None
             if mc is not None and sum(mc) >= L:
                 mc = None
+            dp = self.drop_path_of(bs)
+            if dp > 0 and _STATE.get("fp8"):
+                raise NotImplementedError("stochastic depth (drop_path > 0) in training is not implemented in the fp8 "
+                                          "compute mode; use bf16 or fp32")
             # 2. the attention half, x1 = x + attn(LN1(x)) (the library runs a block without an inner cut whole)
             nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut, mc) if native and pre[bi] is not None else None
+            dpa = dpm = None
             if nt is None:
-                x1, mu1, rs1, sa = self._attn_half_fwd(bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre[bi])
+                x1, mu1, rs1, sa = self._attn_half_fwd(bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre[bi], branch=dp > 0)
+                if dp > 0:                    # x1 holds the branch: the sum goes back into it
+                    dpa = (dp, _seed())
+                    x1 = K.drop_path_add(x, x1, B, L, D, dp, dpa[1], out=x1)
             elif mc is not None:
                 x1 = nt.f32("x1", M, D)
             # 3. the cut between the halves, to the rows the next block reads: everything from here on is row-wise
@@ -1369,8 +1397,12 @@ class EncoderOp:
                 M = B * L
             # 4. the MLP half, x2 = x1 + mlp(LN2(x1)), and the block's tape
             if nt is None:
-                xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
+                xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok, branch=dp > 0)
+                if dp > 0:                    # (L: the rows of this half, behind mcut)
+                    dpm = (dp, _seed())
+                    x2 = K.drop_path_add(x1, x2, B, L, D, dp, dpm[1], out=x2)
                 tapes.append(_Tape(x, mu1, rs1, (g1, b1), sa, x1, mu2, rs2, (g2, b2), sm, pa, pm, cut, mcut))
+                tapes[-1].dpa, tapes[-1].dpm = dpa, dpm
                 x = x2
                 continue
             if mcut is not None:
@@ -1384,28 +1416,35 @@ class EncoderOp:
             x = nt.f32("x2", M, D) if nt.mlp_in_tape else x2
         return x.reshape(B, L, D), (tapes, B, L_in, D)
 
-    def _attn_half_fwd(self, bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre):
-        """LayerNorm 1 and the attention chain on the B * L rows of x (the Python chains)."""
+    def drop_path_of(self, bs) -> float:
+        """The stochastic depth rate in force for both halves of block bs: its rate in training mode, else 0."""
+        return bs.drop_path if self.training else 0.0
+
+    def _attn_half_fwd(self, bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre, branch=False):
+        """LayerNorm 1 and the attention chain on the B * L rows of x (the Python chains).  branch: the chain runs
+        without its residual and the first result is attn(LN1(x)) alone (a dropped half)."""
         M = B * L
         kw = {"pre": pre} if pre is not None else {}
+        res = None if branch else x
         if fuse_ok and M <= 16384 and isinstance(bs.attn, (MHLAChain, DenseChain)):
             o1 = [None, None, None]
-            x1, sa = bs.attn.fwd(None, pa, B, L, x, self.mask, self.training, ln=(x, g1.detach(), b1.detach(), o1), **kw)
+            x1, sa = bs.attn.fwd(None, pa, B, L, res, self.mask, self.training, ln=(x, g1.detach(), b1.detach(), o1), **kw)
             xn1, mu1, rs1 = o1
         else:
             xn1, mu1, rs1 = K.layernorm_fwd(x, D, g1, b1, M, D, cdt, q8=_q8_request(bs.attn, pa, "fwd", D))
-            x1, sa = bs.attn.fwd(xn1, pa, B, L, x, self.mask, self.training, **kw)
+            x1, sa = bs.attn.fwd(xn1, pa, B, L, res, self.mask, self.training, **kw)
         return x1, mu1, rs1, sa
 
-    def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, fuse_ok):
-        """LayerNorm 2 and the MLP chain on the M rows of x1 (the Python chains)."""
+    def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, fuse_ok, branch=False):
+        """LayerNorm 2 and the MLP chain on the M rows of x1 (the Python chains).  branch: as in _attn_half_fwd."""
+        res = None if branch else x1
         if fuse_ok and M <= 16384 and isinstance(bs.mlp, MLPChain):
             o2 = [None, None, None]
-            x2, sm = bs.mlp.fwd(None, pm, x1, self.training, ln=(x1, g2.detach(), b2.detach(), o2))
+            x2, sm = bs.mlp.fwd(None, pm, res, self.training, ln=(x1, g2.detach(), b2.detach(), o2))
             xn2, mu2, rs2 = o2
         else:
             xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
-            x2, sm = bs.mlp.fwd(xn2, pm, x1, self.training)
+            x2, sm = bs.mlp.fwd(xn2, pm, res, self.training)
         return xn2, mu2, rs2, sm, x2
 
     def _fwd_native(self, bs, p, x, B, L, D, pre, cut, mc):
@@ -1419,7 +1458,7 @@ class EncoderOp:
         g1, b1, pa, g2, b2, pm = p
         if not (isinstance(at, MHLAChain) and isinstance(ml, MLPChain)) or (len(pa), len(pm)) != (len(at.names), len(ml.names)):
             return None
-        if self.training and (at.p_attn > 0 or at.p_proj > 0 or ml.p > 0):
+        if self.training and (at.p_attn > 0 or at.p_proj > 0 or ml.p > 0) or self.drop_path_of(bs) > 0:
             return None
         (wqkv, bqkv, wl, bl, wp, bp), (w1, c1, w2, c2) = pa, pm
         Hd = w1.shape[0]
@@ -1552,12 +1591,14 @@ class EncoderOp:
         # the mask of the attention branch's output dropout (a native forward had none: its attention views stay
         # unmade); fp8 mode: the copy feeds this block's proj input-gradient GEMM as its dY -- consumed as it is
         # written, since a branch with output dropout gets it pre-masked
-        pd = (0.0, 0) if tp.native else bs.attn.out_dropout(tp.sa)
-        g, g_lp, dg2, db2 = self._ln_bwd(dxn2, tp.x1, tp.ln2, tp.mu2, tp.rs2, g, pd, want_lp=tp.mcut is None,
+        # (a dropped attention half makes its own copy from the stream gradient, K.drop_path_bwd: none is written here)
+        pd = (0.0, 0) if tp.native or tp.dpa is not None else bs.attn.out_dropout(tp.sa)
+        g, g_lp, dg2, db2 = self._ln_bwd(dxn2, tp.x1, tp.ln2, tp.mu2, tp.rs2, g, pd,
+                                         want_lp=tp.mcut is None and tp.dpa is None,
                                          q8=_q8_request(bs.attn, tp.pa, "bwd", g.shape[1]))
         return g, g_lp, [dg2, db2], gm, dxn2.dtype, None
 
-    def _attn_half_bwd(self, bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed):
+    def _attn_half_bwd(self, bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed, want_lp=True):
         """Backward of x1 = x + attn(LN1(x)) on the block's rows, likewise.  pd_n / q8n: what the low-precision copy
         of the result has to carry for the block below.  Returns (gradient of x, its low-precision copy or None where
         a row cut follows, [dgamma1, dbeta1], the chain's parameter gradients, the dtype of that copy)."""
@@ -1567,13 +1608,15 @@ class EncoderOp:
             return g, g_lp, [None, None], ga, torch.bfloat16
         sa = tp.sa
         dxn1, ga = bs.attn.bwd(sa, g_lp, premasked=bs.attn.out_dropout(sa)[0] > 0)
-        g, g_lp, dg1, db1 = self._ln_bwd(dxn1, tp.x, tp.ln1, tp.mu1, tp.rs1, g, pd_n, q8=q8n, want_lp=tp.cut is None)
+        g, g_lp, dg1, db1 = self._ln_bwd(dxn1, tp.x, tp.ln1, tp.mu1, tp.rs1, g, pd_n, q8=q8n,
+                                         want_lp=want_lp and tp.cut is None)
         return g, g_lp, [dg1, db1], ga, dxn1.dtype
 
     def bwd(self, saved, dy, needs):
         tapes, B, L, D = saved
         g = dy.reshape(-1, D)
-        g_lp = _as_cdt(g)
+        cdt = get_compute_dtype()
+        g_lp = g if tapes and tapes[-1].dpm is not None else _as_cdt(g)      # (a dropped half makes its own copy)
         grads = []
         begin_wgrads(per_block=any(tp.cut is not None or tp.mcut is not None for tp in tapes))
         begin_deferred()
@@ -1597,24 +1640,34 @@ class EncoderOp:
                 # what the low-precision copy of this block's input gradient has to carry for the block below
                 # (a native tape there: no dropout was active and the mode is bf16, so nothing)
                 pd_n, q8n = (0.0, 0), None
-                if ntp is not None and not ntp.native:
+                if ntp is not None and not ntp.native and ntp.dpm is None:
                     pd_n = nbs.mlp.out_dropout(ntp.sm)
                     q8n = _q8_request(nbs.mlp, ntp.pm, "bwd", D)       # the next block's fc2 input-gradient GEMM
+                # the block below starts with a dropped half: it makes its copy itself, none is written for it
+                lp_below = ntp is not None and ntp.dpm is None
                 nat_ok = (tp.native and not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"]
                           and _native_blocks_on())
                 whole = self._bwd_native(bs, tp, g, g_lp) if nat_ok and tp.mcut is None else None
                 if whole is not None:         # the block without an inner cut: ONE library call
                     (g, g_lp, ga, gm), ln1_g, ln2_g, lp_dt = whole, [None, None], [None, None], torch.bfloat16
                 else:
+                    if tp.dpm is not None:
+                        # a dropped MLP half: its branch gradient is the stream gradient scaled per sample, under the
+                        # mask of the branch's output dropout; the stream gradient itself goes on unscaled (dres)
+                        g_lp = K.drop_path_bwd(g, cdt, B, g.shape[0] // B, D, *tp.dpm, lp_drop=bs.mlp.out_dropout(tp.sm))
+                        premasked = True
                     g, g_lp, ln2_g, gm, lp_dt, handed = self._mlp_half_bwd(bs, tp, g, g_lp, premasked, nat_ok)
                     if tp.mcut is not None:
                         # the MLP half ran on the rows the block above reads: back to this block's rows
-                        g, g_lp = expand(g, tp.mcut, lp_dt if g.dtype != lp_dt else None)
-                    g, g_lp, ln1_g, ga, lp_dt = self._attn_half_bwd(bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed)
+                        g, g_lp = expand(g, tp.mcut, lp_dt if g.dtype != lp_dt and tp.dpa is None else None)
+                    if tp.dpa is not None:
+                        g_lp = K.drop_path_bwd(g, cdt, B, g.shape[0] // B, D, *tp.dpa, lp_drop=bs.attn.out_dropout(tp.sa))
+                    g, g_lp, ln1_g, ga, lp_dt = self._attn_half_bwd(bs, tp, g, g_lp, pd_n, q8n, nat_ok, handed,
+                                                                    want_lp=lp_below or ntp is None)
                 premasked = pd_n[0] > 0
                 if tp.cut is not None:
                     # this block ran on its (head, tail) rows: back to the rows of the block below
-                    g, g_lp = expand(g, tp.cut, lp_dt if ntp is not None and g.dtype != lp_dt else None)
+                    g, g_lp = expand(g, tp.cut, lp_dt if lp_below and g.dtype != lp_dt else None)
                 if flush_wgrads(force=False, next_rows=(tp.rows, ntp.rows) if ntp is not None else None) \
                         and _STATE["grad_ready"] is not None:
                     flush_deferred()

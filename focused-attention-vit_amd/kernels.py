@@ -839,6 +839,38 @@ def dropout(x, p, seed):
     return y
 
 
+_U64 = (1 << 64) - 1
+
+
+def drop_path_add(x, y, B, n, D, p, seed, out=None):
+    """x + (keep(b) ? y / (1 - p) : 0) per sample b (favit_drop_path_add): x fp32 [B*n, D], y [B*n, D] fp32 or bf16,
+    both contiguous.  out: None (a new tensor), x or y (in place; y only in fp32)."""
+    require_gpu(x, y, out)
+    if x.dtype != torch.float32 or not x.is_contiguous() or not y.is_contiguous() or x.numel() != B * n * D \
+            or y.numel() != x.numel():
+        raise ValueError("drop_path_add expects contiguous [B*n, D] tensors, x in fp32")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError("drop_path_add: out is a contiguous fp32 [B*n, D] tensor")
+    _abi.check(_abi.lib().favit_drop_path_add(_p(x), _p(y), dt(y), _p(out), B, n, D, float(p), int(seed) & _U64, _st()),
+               "favit_drop_path_add")
+    return out
+
+
+def drop_path_bwd(g, lp_dtype, B, n, D, p, seed, lp_drop=(0.0, 0)):
+    """The branch gradient of a drop-path residual add in the compute dtype lp_dtype (favit_drop_path_bwd):
+    keep(b) ? g / (1 - p) : 0 per sample b, times the element mask lp_drop = (p, seed) of the branch's output dropout
+    (as layernorm_bwd's lp copy carries it).  g fp32 [B*n, D] contiguous."""
+    require_gpu(g)
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != B * n * D:
+        raise ValueError("drop_path_bwd expects a contiguous fp32 [B*n, D] tensor")
+    g_lp = torch.empty((B * n, D), dtype=lp_dtype, device=g.device)
+    _abi.check(_abi.lib().favit_drop_path_bwd(_p(g), _p(g_lp), dt(lp_dtype), B, n, D, float(p), int(seed) & _U64,
+                                              float(lp_drop[0]), int(lp_drop[1]) & _U64, _st()), "favit_drop_path_bwd")
+    return g_lp
+
+
 def sppp_map_patches(seg, P):
     require_gpu(seg)
     if seg.dtype != torch.int64:

@@ -62,9 +62,10 @@ class MHLATransformerBlock(nn.Module):
         mlp_hidden_dim = int(embed_dim * mlp_ratio)
         self.mlp = nn.Sequential(nn.Linear(embed_dim, mlp_hidden_dim), nn.GELU(), nn.Dropout(dropout),
                                  nn.Linear(mlp_hidden_dim, embed_dim), nn.Dropout(dropout))
+        self.drop_path = 0.0                   # stochastic depth rate of both residual branches (set_drop_path_rate)
 
     def _spec(self):
-        return F.BlockSpec(self.attn._chain(), F.MLPChain(self.mlp[2].p, "0", "3"))
+        return F.BlockSpec(self.attn._chain(), F.MLPChain(self.mlp[2].p, "0", "3"), drop_path=self.drop_path)
 
     def forward(self, x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         spec = self._spec()

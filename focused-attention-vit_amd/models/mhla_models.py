@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F
-from .vit import PatchEmbedding, embed_dropout, run_encoder
+from .vit import PatchEmbedding, embed_dropout, run_encoder, set_drop_path_rate
 from .sppp import (SuperpixelSegmentation, PatchToSuperpixelMapper, SuperpixelPooling, DynamicPositionalEncoding,
                    calculate_superpixel_centroids, sppp_tokens)
 from .mhla import MHLATransformerBlock
@@ -70,6 +70,8 @@ class PretrainedViTWithMHLA(nn.Module):
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
+    set_drop_path_rate = set_drop_path_rate
+
 
 class PretrainedSPPPViTWithMHLA(nn.Module):
     """reference models/mhla_models.py:178-395"""
@@ -118,3 +120,5 @@ class PretrainedSPPPViTWithMHLA(nn.Module):
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    set_drop_path_rate = set_drop_path_rate

@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F
-from .vit import PatchEmbedding, run_encoder
+from .vit import PatchEmbedding, run_encoder, set_drop_path_rate
 from .vit_mhla import TransformerBlock          # byte-identical logic in the reference (sppp_mhla.py:21-110)
 from .sppp import (SuperpixelSegmentation, PatchToSuperpixelMapper, SuperpixelPooling, DynamicPositionalEncoding,
                    calculate_superpixel_centroids, sppp_tokens)
@@ -71,3 +71,5 @@ class SPPPViTMHLA(nn.Module):
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    set_drop_path_rate = set_drop_path_rate

@@ -92,13 +92,36 @@ class TransformerBlock(nn.Module):
         self.norm2 = nn.LayerNorm(embed_dim)
         self.mlp = MLP(in_features=embed_dim, hidden_features=int(embed_dim * mlp_ratio), out_features=embed_dim,
                        dropout=dropout)
+        self.drop_path = 0.0                   # stochastic depth rate of both residual branches (set_drop_path_rate)
 
     def _spec(self):
-        return F.BlockSpec(self.attn._chain(), self.mlp._chain())
+        return F.BlockSpec(self.attn._chain(), self.mlp._chain(), drop_path=self.drop_path)
 
     def forward(self, x):
         spec = self._spec()
         return F.run(F.EncoderOp([spec], None, self.training), [x], params(self, spec.names))
+
+
+def drop_path_rates(drop_path_rate: float, depth: int):
+    """Stochastic depth rates of a stack of `depth` blocks, timm's linear rule: block i gets
+    drop_path_rate * i / max(1, depth - 1), so block 0 gets 0 and the last block the full rate."""
+    return [float(drop_path_rate) * i / max(1, depth - 1) for i in range(depth)]
+
+
+def set_drop_path_rate(model, drop_path_rate: float = 0.0):
+    """Stochastic depth (DropPath) for a model that owns a block stack (`model.blocks`): in training mode, block i
+    drops each of its two residual branches per sample with probability drop_path_rates(...)[i] and scales the
+    survivors by 1 / (1 - p) (functional.EncoderOp).  The rate is a plain float attribute `drop_path` of every block,
+    read by its _spec(): no parameter, no buffer, no state_dict key.  It is set here and not by a constructor keyword
+    because the constructors mirror the reference's signatures exactly.  Every model class with a block stack has this
+    function as a method; returns the model, so `Model(...).set_drop_path_rate(0.1)` reads as one expression."""
+    if not 0.0 <= float(drop_path_rate) < 1.0:
+        raise ValueError("drop_path_rate must lie in [0, 1)")
+    blocks = list(model.blocks)
+    for blk, p in zip(blocks, drop_path_rates(drop_path_rate, len(blocks))):
+        blk.drop_path = p
+    model.drop_path_rate = float(drop_path_rate)
+    return model
 
 
 def run_encoder(blocks, x, mask, training, cls_only=False):
@@ -191,3 +214,5 @@ class VisionTransformer(nn.Module):
 
     def get_num_parameters(self):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    set_drop_path_rate = set_drop_path_rate

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F, params
-from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder
+from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder, set_drop_path_rate
 from .mhla import MultiHeadLatentAttention
 
 
@@ -28,13 +28,14 @@ class TransformerBlock(nn.Module):
                        dropout=dropout)
         self.use_mhla = use_mhla
         self._num_heads = num_heads
+        self.drop_path = 0.0                   # stochastic depth rate of both residual branches (set_drop_path_rate)
 
     def _spec(self):
         if self.use_mhla:
             attn = self.attn._chain()
         else:
             attn = F.DenseChain(self._num_heads, self.attn.dropout, 0.0, torch_mha=True)
-        return F.BlockSpec(attn, self.mlp._chain())
+        return F.BlockSpec(attn, self.mlp._chain(), drop_path=self.drop_path)
 
     def forward(self, x: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         spec = self._spec()
@@ -100,3 +101,5 @@ class VisionTransformerMHLA(nn.Module):
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    set_drop_path_rate = set_drop_path_rate

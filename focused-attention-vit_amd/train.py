@@ -811,7 +811,9 @@ class GraphedStep:
         self.segments = max(1, int(segments))
         for s in syncs:
             s.defer = True                     # nothing goes out while capturing / replaying: launches are explicit
-        uses_dropout = model.training and any(isinstance(m, torch.nn.Dropout) and m.p > 0 for m in model.modules())
+        # (stochastic depth draws with the same generator: a block's plain float attribute drop_path)
+        uses_dropout = model.training and any((isinstance(m, torch.nn.Dropout) and m.p > 0) or
+                                              float(getattr(m, "drop_path", 0.0) or 0.0) > 0 for m in model.modules())
         self.epoch = None
         if uses_dropout:
             self.epoch = F.get_dropout_epoch()

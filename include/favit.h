@@ -549,6 +549,25 @@ int favit_mhla_block_attn_bwd(const favit_mhla_block_t* desc, const favit_mhla_b
  * 102, mhla.py:159); the mask is recomputed from (seed, index) in backward. */
 int favit_dropout(const void* x, void* y, int dtype, int64_t n, float p, uint64_t seed, void* stream);
 
+/* Stochastic depth (DropPath; additive in ABI 8; csrc/drop_path.hip): per sample b a residual
+ * branch is dropped with probability p and the survivors are scaled by scale = 1.0f / (1.0f - p).  Sample b is kept
+ * iff the library's dropout draw keeps index b under (seed, p): the index is the sample number and nothing else, and
+ * the dropout epoch word is mixed into the seed as in every other drawing kernel.
+ * Both refuse p outside [0, 1), non-positive sizes and NULL pointers with FAVIT_ERR_INVALID, and D % 8 != 0 (every
+ * access is 16 bytes wide) or n * D >= 2^31 with FAVIT_ERR_UNSUPPORTED; nothing is launched then.
+ *
+ * out[b, r, :] = x[b, r, :] + (keep(b) ? scale * y[b, r, :] : 0)      b < B, r < n
+ * x, out: fp32 [B*n, D] contiguous; y: [B*n, D] of y_dtype (FAVIT_F32 | FAVIT_BF16).
+ * out may alias y (same dtype) or x.  Rows of a dropped sample are NOT read from y. */
+int favit_drop_path_add(const float* x, const void* y, int y_dtype, float* out, int32_t B, int32_t n, int32_t D,
+                        float p, uint64_t seed, void* stream);
+/* g_lp[b, r, :] = (lp_dtype) (keep(b) ? scale * g[b, r, :] : 0), optionally also times the element dropout mask of
+ * the branch's output dropout (lp_dropout_p / _seed, element index row*D + col and scaling exactly as
+ * favit_layernorm_bwd's lp copy).  g: fp32 [B*n, D]; g_lp: [B*n, D] of lp_dtype (FAVIT_F32 | FAVIT_BF16).
+ * Rows of a dropped sample are NOT read from g. */
+int favit_drop_path_bwd(const float* g, void* g_lp, int lp_dtype, int32_t B, int32_t n, int32_t D, float p,
+                        uint64_t seed, float lp_dropout_p, uint64_t lp_dropout_seed, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * SPPP (models/sppp.py, models/sppp_mhla.py); the label map [B,HW,HW] int64 is an input.
  * map_patches (sppp.py:91-128): dominant label per patch (max count, ties -> smallest

@@ -63,14 +63,15 @@ def build_model(pkg, a, classes):
     M = pkg.models
     kw = dict(img_size=a.img_size, patch_size=a.patch_size, num_classes=classes, embed_dim=a.embed_dim, depth=a.depth,
               num_heads=a.num_heads, dropout=a.dropout)
+    rate = getattr(a, "drop_path", 0.0)
     if a.experiment == "traditional":
-        return M.vit.VisionTransformer(**kw)
+        return M.vit.VisionTransformer(**kw).set_drop_path_rate(rate)
     if a.experiment in ("mhla", "mhla_pretrained"):
-        return M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True, **kw)
+        return M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True, **kw).set_drop_path_rate(rate)
     model = M.sppp_mhla.SPPPViTMHLA(num_superpixels=a.num_superpixels, pooling_type=a.pooling_type,
                                     window_size=a.window_size, use_mhla=True, **kw)
     model.segmentation.compactness = a.compactness
-    return model
+    return model.set_drop_path_rate(rate)
 
 
 def prepare_pretrained(model, weights=None, freeze_layers=False):
@@ -146,6 +147,9 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--num_heads", type=int, default=12)
     ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--drop_path", type=float, default=0.0, metavar="RATE",
+                    help="stochastic depth: the last block drops each residual branch per sample with this probability, "
+                         "block i of depth with RATE * i / (depth - 1) (set_drop_path_rate; not fp8)")
     ap.add_argument("--num_superpixels", type=int, default=16)
     ap.add_argument("--compactness", type=float, default=0.1)
     ap.add_argument("--pooling_type", default="mean", choices=["mean", "max", "attention"])
