@@ -176,6 +176,7 @@ _SIGS = {
     "favit_randaugment": ([vp, vp, vp, vp, vp, i32, vp, C.POINTER(f32), i32, u64, i32, i32, i32, C.POINTER(f32),
                            C.POINTER(f32), vp], C.c_int),
     "favit_random_erase": ([vp, vp, C.POINTER(f32), i32, u64, i32, i32, i32, i32, vp], C.c_int),
+    "favit_cross_entropy_distill": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, i32, vp], C.c_int),
 }
 
 _lib = None

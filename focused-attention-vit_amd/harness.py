@@ -108,7 +108,7 @@ def evaluate(model, loader: Iterable, batch_size: Optional[int] = None) -> Dict[
 def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer, epochs: int,
         log: Callable[[str], None] = print, label_smoothing: float = 0.0, schedule=None,
         checkpoint: Optional[str] = None, checkpoint_every: int = 1, resume: bool = False,
-        eval_ema: bool = False) -> Dict[str, object]:
+        eval_ema: bool = False, teacher=None, distill: Optional["T.Distill"] = None) -> Dict[str, object]:
     """The reference's epoch loop (experiments/mhla_pretrained.py:350-420) with device-side statistics: one host
     sync per EPOCH.  optimizer: train.FusedAdamW (hot path) or any torch.optim optimizer.
     label_smoothing: the TRAINING loss is nn.CrossEntropyLoss(label_smoothing=...)'s; evaluation keeps the plain one.
@@ -124,12 +124,21 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
     transform's generator and the shuffle epoch of datasets.batches).  Needs a train.FusedAdamW.
     resume: with an existing `checkpoint` file, load it and continue from the stored epoch; the history is extended,
     not restarted, and total_training_time covers this process only.  Under data parallelism rank 0 writes.
-    eval_ema: the validation pass runs inside optimizer.ema_weights() (train.FusedAdamW with ema_decay)."""
+    eval_ema: the validation pass runs inside optimizer.ema_weights() (train.FusedAdamW with ema_decay).
+    teacher, distill: a frozen model and a train.Distill; the training loss is then the distilled one on the teacher's
+    logits for the same (mixed) images (train.teacher_logits, train.cross_entropy), and history["train_kd"] is the
+    epoch mean of the teacher term, summed on the device (no sync of its own).  Evaluation never uses the teacher.  The
+    teacher is not part of the checkpoint -- it is frozen, and the caller rebuilds it before resuming.  Without a
+    teacher the loop is the one of before and the history has no such key."""
     dev = next(model.parameters()).device
     hist: Dict[str, List[float]] = {"train_loss": [], "train_acc": [], "val_loss": [], "val_acc": [], "epoch_time": []}
     track_norm = getattr(optimizer, "grad_norm", None) is not None
     if track_norm:
         hist["grad_norm"] = []
+    T._check_teacher(teacher, distill)
+    if teacher is not None:
+        hist["train_kd"] = []
+        T._check_teacher_frozen(teacher, optimizer)
     if checkpoint is not None and not isinstance(optimizer, T.FusedAdamW):
         raise TypeError("fit: checkpoint= needs a train.FusedAdamW (its state is saved by parameter name)")
     if checkpoint is not None and checkpoint_every < 1:
@@ -152,13 +161,20 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         correct = torch.zeros((), device=dev, dtype=torch.int64)
         total = n_batches = 0
         norm_sum = torch.zeros((), device=dev) if track_norm else None
+        kd_sum = torch.zeros((), device=dev) if teacher is not None else None
         for images, labels in train_loader:
             mix_lam = None
             if isinstance(labels, MixedLabels):
                 labels, mix_lam = labels
             optimizer.zero_grad()
-            out = model(images)
-            loss = T.cross_entropy(out, labels, label_smoothing, mix_lam)
+            if teacher is None:
+                out = model(images)
+                loss = T.cross_entropy(out, labels, label_smoothing, mix_lam)
+            else:
+                t_logits = T.teacher_logits(teacher, images)
+                out = model(images)
+                loss, kd = T.cross_entropy_distill(out, labels, t_logits, distill, label_smoothing, mix_lam)
+                kd_sum += kd
             loss.backward()
             optimizer.step()
             if schedule is not None:
@@ -173,6 +189,8 @@ def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer
         hist["train_acc"].append(100.0 * correct.item() / max(1, total))
         if track_norm:
             hist["grad_norm"].append(norm_sum.item() / max(1, n_batches))
+        if teacher is not None:
+            hist.setdefault("train_kd", []).append(kd_sum.item() / max(1, n_batches))
         if val_loader is not None:
             if eval_ema:
                 with optimizer.ema_weights():

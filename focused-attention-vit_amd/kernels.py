@@ -1090,11 +1090,71 @@ def random_erase(x, box, value=0.0, seed=0):
     return x
 
 
-def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0, mix_lam=None):
+def _check_distill(logits, teacher, alpha, tau, hard):
+    """Argument checks of the distilled loss, before the library is touched."""
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"cross_entropy: distill_alpha must be in [0, 1], got {alpha}")
+    if not hard and not (math.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"cross_entropy: distill_tau must be a finite number > 0, got {tau}")
+    if not isinstance(teacher, torch.Tensor):
+        raise TypeError("cross_entropy: teacher must be a tensor of teacher logits")
+    if teacher.dtype != torch.float32 or tuple(teacher.shape) != tuple(logits.shape) or not teacher.is_contiguous():
+        raise TypeError(f"cross_entropy: teacher must be a contiguous fp32 tensor of the logits' shape "
+                        f"{tuple(logits.shape)}, got {teacher.dtype} {tuple(teacher.shape)}")
+    if teacher.device != logits.device:
+        raise ValueError(f"cross_entropy: teacher is on {teacher.device}, the logits on {logits.device}")
+
+
+def cross_entropy_distill(logits, teacher, labels, grad_scale=None, label_smoothing=0.0, mix_lam=None, alpha=0.5,
+                          tau=1.0, hard=False):
+    """favit_cross_entropy_distill: returns (loss_rows[B], dlogits or None, kd_rows[B]) with
+    loss_rows = (1 - alpha) * base + alpha * kd, base the row kernels.cross_entropy gives for the same labels,
+    label_smoothing and mix_lam, and kd the distance to the teacher's logits (fp32 [B, C], no gradient):
+    soft, tau^2 * KL(softmax(teacher / tau) || softmax(logits / tau)); hard, the cross-entropy against the teacher's
+    argmax (lowest index on ties; tau unused).  dlogits is the gradient of the weighted sum with respect to the
+    logits alone.  alpha = 0 is the loss without a teacher, bit for bit; kd_rows is then zero."""
+    alpha, tau, hard = float(alpha), float(tau), bool(hard)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 \
+            or not logits.is_contiguous():
+        raise TypeError("cross_entropy: logits must be a contiguous fp32 [B, C] tensor")
+    _check_distill(logits, teacher, alpha, tau, hard)
+    require_gpu(logits, teacher, labels)
+    B, Cn = logits.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise TypeError("cross_entropy: labels must be a contiguous int64 [B] tensor of class indices "
+                        "(out-of-range labels, e.g. ignore_index = -100, give a NaN loss row)")
+    if mix_lam is not None:
+        require_gpu(mix_lam)
+        if mix_lam.dtype != torch.float32 or tuple(mix_lam.shape) != (B,) or not mix_lam.is_contiguous():
+            raise TypeError("cross_entropy: mix_lam must be a contiguous fp32 [B] tensor")
+    loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
+    kd_rows = (torch.zeros if alpha == 0.0 else torch.empty)(B, dtype=torch.float32, device=logits.device)
+    dlog = torch.empty_like(logits) if grad_scale is not None else None
+    gs = 0.0 if grad_scale is None else grad_scale
+    _abi.check(_abi.lib().favit_cross_entropy_distill(_p(logits), _p(teacher), _p(labels), _p(mix_lam), _p(loss_rows),
+                                                      _p(kd_rows), _p(dlog), B, Cn, gs, float(label_smoothing), alpha,
+                                                      tau, int(hard), _st()), "favit_cross_entropy_distill")
+    return loss_rows, dlog, kd_rows
+
+
+def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0, mix_lam=None, teacher=None,
+                  distill_alpha=0.0, distill_tau=1.0, distill_hard=False):
     """Returns (loss_rows[B], dlogits or None).  label_smoothing = eps in [0, 1): the loss of
     nn.CrossEntropyLoss(label_smoothing=eps) (favit_cross_entropy_ls); 0 calls favit_cross_entropy.
     mix_lam (fp32 [B] on the device, read when the kernel runs): the target of row b is lam[b] * onehot(labels[b]) +
-    (1 - lam[b]) * onehot(labels[B-1-b]), the labels of kernels.batch_mix's pairs (favit_cross_entropy_mix)."""
+    (1 - lam[b]) * onehot(labels[B-1-b]), the labels of kernels.batch_mix's pairs (favit_cross_entropy_mix).
+    teacher (fp32 [B, C] teacher logits): the distilled loss of cross_entropy_distill with distill_alpha / distill_tau /
+    distill_hard, without its kd_rows.  Without a teacher the call is the one of before; a distill_alpha other than 0
+    is then an error."""
+    if teacher is not None:
+        return cross_entropy_distill(logits, teacher, labels, grad_scale, label_smoothing, mix_lam, distill_alpha,
+                                     distill_tau, distill_hard)[:2]
+    if distill_alpha:
+        if not 0.0 <= distill_alpha <= 1.0:
+            raise ValueError(f"cross_entropy: distill_alpha must be in [0, 1], got {distill_alpha}")
+        raise ValueError("cross_entropy: distill_alpha > 0 needs teacher logits")
     if not 0.0 <= label_smoothing < 1.0:
         raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
     require_gpu(logits, labels)

@@ -35,12 +35,109 @@ class _CrossEntropyFn(torch.autograd.Function):
         return dlog * g, None, None, None
 
 
+class Distill:
+    """How a frozen teacher enters the loss: loss = (1 - alpha) * base + alpha * kd, with base the cross-entropy of the
+    labels (smoothed, mixed) and kd the distance to the teacher's logits.  kind "soft": tau^2 * KL(softmax(z / tau) ||
+    softmax(x / tau)) per row (Hinton's loss; DeiT's code divides by the class count on top, a factor a caller folds
+    into alpha); kind "hard": the cross-entropy against the teacher's argmax (tau unused).  Validates on construction."""
+    __slots__ = ("alpha", "tau", "kind")
+
+    def __init__(self, alpha: float, tau: float = 1.0, kind: str = "soft"):
+        if kind not in ("soft", "hard"):
+            raise ValueError(f"Distill: kind must be 'soft' or 'hard', got {kind!r}")
+        alpha, tau = float(alpha), float(tau)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"Distill: alpha must be in [0, 1], got {alpha}")
+        if not (tau == tau and tau not in (float("inf"), float("-inf")) and tau > 0.0):
+            raise ValueError(f"Distill: tau must be a finite number > 0, got {tau}")
+        self.alpha, self.tau, self.kind = alpha, tau, kind
+
+    @property
+    def hard(self) -> bool:
+        return self.kind == "hard"
+
+    def __repr__(self):
+        return f"Distill(alpha={self.alpha}, tau={self.tau}, kind={self.kind!r})"
+
+
+class _DistillFn(torch.autograd.Function):
+    """The distilled loss (mean reduction) forward + gradient in one kernel; the second output is the mean of kd_rows
+    (for logging, no gradient).  The teacher's logits get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_smoothing, mix_lam, teacher_logits, alpha, tau, hard):
+        B = logits.shape[0]
+        rows, dlog, kd = K.cross_entropy_distill(logits.contiguous(), teacher_logits, labels.contiguous(),
+                                                 grad_scale=1.0 / B, label_smoothing=label_smoothing, mix_lam=mix_lam,
+                                                 alpha=alpha, tau=tau, hard=hard)
+        ctx.save_for_backward(dlog)
+        sums = K.reduce_rows(torch.stack((rows, kd), 1))
+        kd_mean = sums[1] / B
+        ctx.mark_non_differentiable(kd_mean)
+        return sums[0] / B, kd_mean
+
+    @staticmethod
+    def backward(ctx, g, _g_kd):
+        (dlog,) = ctx.saved_tensors
+        return dlog * g, None, None, None, None, None, None, None
+
+
+def cross_entropy_distill(logits: torch.Tensor, labels: torch.Tensor, teacher_logits: torch.Tensor, distill: Distill,
+                          label_smoothing: float = 0.0, mix_lam: Optional[torch.Tensor] = None):
+    """(loss, kd): the distilled loss of `cross_entropy` and the mean of the rows' teacher term (a device scalar without
+    a gradient, for logging)."""
+    if not isinstance(distill, Distill):
+        raise TypeError(f"cross_entropy: distill must be a train.Distill, got {type(distill).__name__}")
+    if teacher_logits is None:
+        raise ValueError("cross_entropy: distill= needs teacher_logits")
+    t = teacher_logits.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return _DistillFn.apply(logits, labels, float(label_smoothing), mix_lam, t, distill.alpha, distill.tau, distill.hard)
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0,
-                  mix_lam: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  mix_lam: Optional[torch.Tensor] = None, teacher_logits: Optional[torch.Tensor] = None,
+                  distill: Optional[Distill] = None) -> torch.Tensor:
     """nn.CrossEntropyLoss(label_smoothing=label_smoothing)(logits, labels), mean reduction.
     mix_lam (fp32 [B] on the device, no gradient): the loss against the Mixup / CutMix target of data.BatchMix,
-    lam[b] * onehot(labels[b]) + (1 - lam[b]) * onehot(labels[B-1-b]), smoothed on top; None: the plain loss."""
-    return _CrossEntropyFn.apply(logits, labels, float(label_smoothing), mix_lam)
+    lam[b] * onehot(labels[b]) + (1 - lam[b]) * onehot(labels[B-1-b]), smoothed on top; None: the plain loss.
+    distill (a Distill) with teacher_logits ([B, C], detached here: the gradient goes to `logits` only): the mean of
+    (1 - alpha) * that loss's row + alpha * the row's distance to the teacher (favit_cross_entropy_distill).
+    distill=None is the call of before, whatever teacher_logits holds."""
+    if distill is None:
+        return _CrossEntropyFn.apply(logits, labels, float(label_smoothing), mix_lam)
+    return cross_entropy_distill(logits, labels, teacher_logits, distill, label_smoothing, mix_lam)[0]
+
+
+def _check_teacher_frozen(teacher: torch.nn.Module, opt) -> None:
+    """Raise if a teacher parameter with requires_grad=True sits in `opt` (a FusedAdamW or a torch optimizer)."""
+    if any(p.requires_grad for p in teacher.parameters()):
+        owned = set()
+        for g in getattr(opt, "groups", None) or getattr(opt, "param_groups", ()):
+            flat = g.get("flat") if isinstance(g, dict) else None
+            for p in (flat.params if flat is not None else g.get("params", ())):
+                owned.add(id(p))
+        for n, p in teacher.named_parameters():
+            if p.requires_grad and id(p) in owned:
+                raise ValueError(f"teacher_logits: teacher parameter {n!r} requires grad and is in the optimizer; "
+                                 "the teacher must be frozen and kept out of it")
+
+
+def teacher_logits(teacher: torch.nn.Module, images: torch.Tensor, opt=None) -> torch.Tensor:
+    """The frozen teacher's fp32 logits for `images`: run in eval() (no dropout, no drop path) under torch.no_grad()
+    (no tape); the teacher's `training` flag is restored.  opt (a FusedAdamW or a torch optimizer): raises if a
+    teacher parameter with requires_grad=True sits in it -- such a teacher would be trained, not distilled from."""
+    if opt is not None:
+        _check_teacher_frozen(teacher, opt)
+    was_training = teacher.training
+    teacher.eval()
+    try:
+        with torch.no_grad():
+            out = teacher(images)
+    finally:
+        teacher.train(was_training)
+    return out.float()
 
 
 def param_groups(model: torch.nn.Module, lr: float, head_lr: Optional[float] = None,
@@ -755,12 +852,25 @@ def load_checkpoint(path: str, model: torch.nn.Module, opt: Optional[FusedAdamW]
     return ck.get("extra")
 
 
-def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0, mix_lam=None):
+def _check_teacher(teacher, distill):
+    if (teacher is None) != (distill is None):
+        raise ValueError("a teacher and a Distill go together: got " +
+                         ("a teacher without distill=" if distill is None else "distill= without a teacher"))
+    if distill is not None and not isinstance(distill, Distill):
+        raise TypeError(f"distill must be a train.Distill, got {type(distill).__name__}")
+
+
+def train_step(model, images, labels, opt: FusedAdamW, label_smoothing: float = 0.0, mix_lam=None, teacher=None,
+               distill: Optional[Distill] = None):
     """One step of the reference's hot loop; returns the (device) loss tensor, no host sync.
-    mix_lam: the target weights of a batch mixed by data.BatchMix (cross_entropy)."""
+    mix_lam: the target weights of a batch mixed by data.BatchMix (cross_entropy).
+    teacher, distill: a frozen model whose logits on the same (mixed) images enter the loss as `distill` says
+    (teacher_logits, cross_entropy); without them the step of before."""
+    _check_teacher(teacher, distill)
     opt.zero_grad()
+    t_logits = teacher_logits(teacher, images, opt) if teacher is not None else None
     logits = model(images)
-    loss = cross_entropy(logits, labels, label_smoothing, mix_lam)
+    loss = cross_entropy(logits, labels, label_smoothing, mix_lam, t_logits, distill)
     loss.backward()
     opt.step()
     return loss
@@ -789,19 +899,33 @@ class GraphedStep:
     * Mixed batches (data.BatchMix): the target weights change every step, so they cannot be a by-value argument.  With
       ``mix=True`` the step owns a static fp32 [B] buffer that the captured loss kernel (favit_cross_entropy_mix) reads
       when it executes; every call copies its ``mix_lam`` into it, and a call without one fills it with ones, which
-      gives the loss and the gradient of the unmixed step bit for bit."""
+      gives the loss and the gradient of the unmixed step bit for bit.
+    * Distillation (``teacher=``, ``distill=``): the frozen teacher's forward (eval mode, no tape) is captured in graph 0
+      between zero_grad and the student's forward, and its logits live in the graphs' pool.  ``distill.alpha``, ``tau``
+      and the kind are by-value kernel arguments frozen into the graph, like ``label_smoothing``: another Distill needs
+      another GraphedStep.  The teacher's compute-dtype weight copies are made during warm-up and kept alive with the
+      step; the teacher is frozen, so they stay valid (after editing its weights, build a new step).  Combines with
+      ``mix=True``.  ``self.kd`` is the mean teacher term of the last replay (a device scalar).  Under data parallelism
+      every rank runs its own replica of the teacher, which takes no part in GradSync; like the rest of the RCCL path
+      this is untested beyond one rank."""
 
     def __init__(self, model: torch.nn.Module, opt: FusedAdamW, images: torch.Tensor, labels: torch.Tensor,
                  warmup: int = 3, segments: Optional[int] = None, static_inputs: bool = False,
-                 label_smoothing: float = 0.0, mix: bool = False):
+                 label_smoothing: float = 0.0, mix: bool = False, teacher: Optional[torch.nn.Module] = None,
+                 distill: Optional[Distill] = None):
         """static_inputs: `images` / `labels` themselves are the buffers the captured kernels read (no clone at capture,
         no copy per call when the step is called with these same tensors): for a producer that writes every batch into
         fixed device buffers (bench.py's resident synthetic batch).  Default: private copies, one device-to-device copy
         of the batch per call."""
         if K.GEMM_TRACE is not None:
             raise RuntimeError("GraphedStep: disable kernels.GEMM_TRACE (event records cannot be captured)")
+        _check_teacher(teacher, distill)
         self.model, self.opt = model, opt
         self.label_smoothing = float(label_smoothing)          # (a by-value kernel argument: frozen into the graph)
+        self.teacher, self.distill = teacher, distill          # (alpha, tau, kind: by value as well)
+        self.kd = None
+        if teacher is not None:
+            _check_teacher_frozen(teacher, opt)
         self.x, self.y = (images, labels) if static_inputs else (images.clone(), labels.clone())
         self.lam = torch.ones(labels.shape[0], dtype=torch.float32, device=labels.device) if mix else None
         syncs = [g["sync"] for g in opt.groups if g["sync"] is not None and g["sync"]._active]
@@ -847,6 +971,8 @@ class GraphedStep:
         # the split-K slab workspace (kernels.py keeps outgrown ones) -- and the installed label maps (their content is
         # changed with SuperpixelSegmentation.update_label_maps; data.DeviceLoader does so once a step is captured).
         self._keep = [K._GROUPED_WS.get(self.x.device.index)]
+        if teacher is not None:        # and the teacher with the compute-dtype copies of its weights (functional.wcast)
+            self._keep += [teacher] + [getattr(p, "_favit_cast", None) for p in teacher.parameters()]
         self._map_states = []          # label maps + the tensors derived from them (models/sppp.py::_MapState)
         for mod in model.modules():
             seg = getattr(mod, "segmentation", None)
@@ -871,11 +997,18 @@ class GraphedStep:
             if self.epoch is not None:
                 self.epoch.add_(1)
             self.opt.zero_grad()
+            t_logits = teacher_logits(self.teacher, self.x) if self.teacher is not None else None
             with F.encoder_segments(self.segments) as seg:
-                loss = cross_entropy(self.model(self.x), self.y, self.label_smoothing, self.lam)
+                if self.distill is None:
+                    loss = cross_entropy(self.model(self.x), self.y, self.label_smoothing, self.lam)
+                else:
+                    loss, kd = cross_entropy_distill(self.model(self.x), self.y, t_logits, self.distill,
+                                                     self.label_smoothing, self.lam)
             bounds = list(seg.boundaries)
         if graphs is not None:
             self.loss = loss
+            if self.distill is not None:
+                self.kd = kd
         heads, grads = [loss], [None]
         for k in range(len(bounds), -1, -1):               # the piece that starts at leaf k-1 (k = 0: the input side)
             if graphs is not None:

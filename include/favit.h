@@ -753,6 +753,37 @@ int favit_randaugment(const uint8_t* src_u8, uint8_t* scratch, float* out, uint8
 int favit_random_erase(float* x, const int32_t* box, const float* value, int32_t normal, uint64_t seed, int32_t B,
                        int32_t C, int32_t H, int32_t W, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Knowledge distillation (additive in ABI 8; csrc/distill.hip): the loss of the labels and the
+ * distance to a frozen teacher's logits in one launch.  x = logits, z = teacher, both fp32 [B, C] contiguous.
+ * ---------------------------------------------------------------------------------- */
+/*   base[b] = the loss row of favit_cross_entropy_mix with the same lam and label_smoothing (lam == NULL: unmixed,
+ *             the row of favit_cross_entropy_ls)
+ *   soft (hard == 0):  kd[b] = tau^2 * sum_c q_c (log q_c - log p_c),  q = softmax(z / tau), p = softmax(x / tau),
+ *             evaluated through the two log-softmaxes, so an underflowed q_c contributes 0 and not 0 * inf
+ *   hard (hard != 0):  kd[b] = lse(x) - x[argmax_c z_c], the lowest index on ties; tau is not used
+ *   loss_rows[b] = (1 - alpha) * base[b] + alpha * kd[b];   kd_rows[b] = kd[b] when kd_rows != NULL (for logging)
+ *   dlogits[b,c] = grad_scale * ((1 - alpha) * (softmax(x)_c - target_c) + alpha * d_c),  target as in
+ *             favit_cross_entropy_mix;  soft: d_c = tau * (p_c - q_c);  hard: d_c = softmax(x)_c - [c == argmax z]
+ * The teacher gets no gradient.  The mean of the soft kd over the rows is Hinton's loss,
+ * kl_div(reduction = 'batchmean') * tau^2.  DeiT's code divides by B * C instead: the two differ by the factor 1 / C,
+ * which a caller who wants DeiT's weighting folds into alpha.
+ * alpha == 0 calls the existing entry point (favit_cross_entropy_mix with lam, else favit_cross_entropy_ls, which at
+ * label_smoothing == 0 is favit_cross_entropy) and so gives its bits; the teacher is not read and kd_rows not written.
+ * Refused with FAVIT_ERR_INVALID before any launch: alpha outside [0, 1]; tau not finite or <= 0 when soft;
+ * label_smoothing outside [0, 1); NULL logits, teacher, labels or loss_rows; B <= 0 or C <= 0.
+ * An own or (with lam) a partner label out of range gives a NaN loss row, never an out-of-range read; every other row
+ * keeps its bits and all of dlogits stays finite.  A non-finite value in teacher row b makes loss_rows[b] (and
+ * kd_rows[b]) NaN; every other row keeps its bits.  Health word as in the sibling loss kernels: a non-finite row whose
+ * labels are valid raises the loss flag.
+ * One launch, one wave per row, four rows per 256-thread workgroup, any C >= 1; no workspace, no atomics other than
+ * the health word.  Rows of 128 < C <= 1024 are read once and held in registers; shorter and longer rows are walked in memory. */
+int favit_cross_entropy_distill(const float* logits, const float* teacher, const int64_t* labels,
+                                const float* lam /* [B] device or NULL: unmixed */,
+                                float* loss_rows, float* kd_rows /* or NULL */, float* dlogits /* or NULL */,
+                                int32_t B, int32_t C, float grad_scale, float label_smoothing,
+                                float alpha, float tau, int32_t hard, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,38 @@ def build_model(pkg, a, classes):
     return model.set_drop_path_rate(rate)
 
 
+def load_flat_weights(model, weights):
+    """Copy a flat state-dict .npz archive (opened without pickle) into the model: a key the archive lacks stays as
+    initialised, a key with another shape is an error.  Returns the names of the keys that were loaded."""
+    loaded = []
+    sd = model.state_dict()
+    with np.load(weights, allow_pickle=False) as arc:
+        for k in arc.files:
+            if k not in sd:
+                continue
+            v = torch.from_numpy(arc[k])
+            if tuple(v.shape) != tuple(sd[k].shape):
+                raise ValueError(f"{weights}: {k} has shape {tuple(v.shape)}, the model's is {tuple(sd[k].shape)}")
+            with torch.no_grad():
+                sd[k].copy_(v)
+            loaded.append(k)
+    return loaded
+
+
+def build_teacher(pkg, a, classes):
+    """--teacher_experiment: a frozen model of the student's dimensions with dropout 0 and no drop path, in eval mode,
+    with --teacher_weights loaded (the flat .npz --weights takes; for mhla_pretrained the same archive serves both:
+    the dense model the student's weights came from supervises it).  On the host, like build_model."""
+    ta = argparse.Namespace(**vars(a))
+    ta.experiment, ta.dropout, ta.drop_path = a.teacher_experiment, 0.0, 0.0
+    teacher = build_model(pkg, ta, classes)
+    loaded = load_flat_weights(teacher, a.teacher_weights) if a.teacher_weights else []
+    for p in teacher.parameters():
+        p.requires_grad = False
+    print(f"teacher: {a.teacher_experiment}, {len(loaded)} tensors loaded from {a.teacher_weights}")
+    return teacher.eval()
+
+
 def prepare_pretrained(model, weights=None, freeze_layers=False):
     """The set-up of the reference's two pre-trained experiments (experiments/mhla_pretrained.py:224-247,
     experiments/sppp_mhla_pretrained.py:236-259).  weights: a flat state-dict .npz archive (opened without pickle);
@@ -81,19 +113,7 @@ def prepare_pretrained(model, weights=None, freeze_layers=False):
     identity (eye weight, zero bias).  freeze_layers: every parameter whose name contains none of head / latent_proj /
     segmentation / patch_mapper / pooling stops training (the last three only occur in the SPPP models, so this is
     both experiments' rule).  Returns the names of the keys that were loaded."""
-    loaded = []
-    if weights:
-        sd = model.state_dict()
-        with np.load(weights, allow_pickle=False) as arc:
-            for k in arc.files:
-                if k not in sd:
-                    continue
-                v = torch.from_numpy(arc[k])
-                if tuple(v.shape) != tuple(sd[k].shape):
-                    raise ValueError(f"{weights}: {k} has shape {tuple(v.shape)}, the model's is {tuple(sd[k].shape)}")
-                with torch.no_grad():
-                    sd[k].copy_(v)
-                loaded.append(k)
+    loaded = load_flat_weights(model, weights) if weights else []
     with torch.no_grad():
         for n, mod in model.named_modules():
             if n.endswith("latent_proj") and isinstance(mod, torch.nn.Linear):
@@ -206,7 +226,26 @@ def parse_args(argv=None):
                          "group (models.sppp.TokenBucketed; the reference -- and this tool without the flag -- fails on "
                          "such a batch in torch.stack, models/sppp_mhla.py:300; any other count fails in the "
                          "positional encoding, there and here)")
-    return ap.parse_args(argv)
+    ap.add_argument("--teacher_experiment", default=None, choices=["traditional", "mhla"],
+                    help="knowledge distillation: a frozen teacher of this kind with the student's dimensions and dropout 0 "
+                         "(default: no teacher)")
+    ap.add_argument("--teacher_weights", default=None,
+                    help="--teacher_experiment: flat state-dict .npz archive, as --weights takes (mhla_pretrained: the same file)")
+    ap.add_argument("--distill_alpha", type=float, default=0.0,
+                    help="training loss = (1 - a) * cross-entropy + a * teacher term (default 0: off; needs a teacher)")
+    ap.add_argument("--distill_tau", type=float, default=1.0, help="--distill_type soft: the temperature")
+    ap.add_argument("--distill_type", default="soft", choices=["soft", "hard"],
+                    help="soft: tau^2 * KL(teacher || student) at temperature tau; hard: cross-entropy against the teacher's argmax")
+    a = ap.parse_args(argv)
+    if not 0.0 <= a.distill_alpha <= 1.0:
+        ap.error("--distill_alpha must be in [0, 1]")
+    if a.distill_alpha > 0 and a.teacher_experiment is None:
+        ap.error("--distill_alpha > 0 needs --teacher_experiment")
+    if a.teacher_weights is not None and a.teacher_experiment is None:
+        ap.error("--teacher_weights needs --teacher_experiment")
+    if not (a.distill_tau > 0 and a.distill_tau != float("inf")):
+        ap.error("--distill_tau must be a finite number > 0")
+    return a
 
 
 def main(argv=None):
@@ -249,6 +288,10 @@ def main(argv=None):
         print(f"pretrained set-up: {len(loaded)} tensors loaded from {a.weights}; trainable parameters {n_train:,} of "
               f"{sum(p.numel() for p in model.parameters()):,}")
     model = model.cuda()
+    teacher = distill = None
+    if a.teacher_experiment is not None and a.distill_alpha > 0:
+        teacher = build_teacher(pkg, a, classes).cuda()
+        distill = pkg.train.Distill(a.distill_alpha, a.distill_tau, a.distill_type)
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
     group_kw, opt_kw = {}, {}          # (none of the three flags: exactly the groups and the optimizer of before)
     if a.layer_decay is not None:
@@ -298,7 +341,7 @@ def main(argv=None):
     with torch.cuda.stream(work):
         res = pkg.harness.fit(run, train_loader, test_loader, opt, a.epochs, label_smoothing=a.label_smoothing,
                               schedule=schedule, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
-                              resume=a.resume, eval_ema=a.eval_ema)
+                              resume=a.resume, eval_ema=a.eval_ema, teacher=teacher, distill=distill)
         if a.eval_ema:
             with opt.ema_weights():
                 ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
