@@ -1,4 +1,9 @@
-"""ctypes binding of libfavit.so (the C ABI declared in include/favit.h).
+"""ctypes binding of libfavit.so, derived from the C ABI declared in include/favit.h.
+
+The header is read at import (the library is not needed for that): every ``FAVIT_X`` constant becomes the module
+attribute ``X`` (F32, BF16, ACT_GELU, ERR_INVALID, ADAMW_MAX_SEGMENTS, ...), every ``favit_*_t`` struct a
+ctypes.Structure (STRUCTS; the five the package fills in also under the names of _STRUCT_NAMES) and every prototype
+an entry of _SIGS.  A declaration the reader does not recognise is an error, never skipped.
 
 The library is built in-tree by ``__graft_entry__.build()`` /
 ``make -C focused-attention-vit_amd/csrc``.  There is NO fallback: if the library is
@@ -14,170 +19,109 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libfavit.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "favit.h")
 
-F32, BF16, FP8 = 0, 1, 2
-F32X3 = 3        # favit_gemm_t.in_dtype only: fp32 operands, three-pass split-bf16 product (include/favit.h)
-E4M3, E5M2 = 0, 1
-ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_SAVEGRAD, ACT_MULAUX = 0, 1, 2, 3, 4
-ERR_INVALID, ERR_UNSUPPORTED, ERR_ALIGN, ERR_LAUNCH = -1, -2, -3, -4
-POOL = {"mean": 0, "max": 1, "attention": 2}
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
+            "uint64_t": C.c_uint64, "float": C.c_float}
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char*": C.c_char_p}
+_STRUCT_NAMES = {"favit_gemm_t": "GemmDesc", "favit_sdpa_t": "SdpaDesc", "favit_mhla_block_t": "BlockDesc",
+                 "favit_mhla_block_mlp_t": "BlockMlp", "favit_adamw_multi_t": "AdamwMulti"}
 
-vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
-
-
-class GemmDesc(C.Structure):
-    """Mirror of favit_gemm_t (include/favit.h)."""
-    _fields_ = [
-        ("A", vp), ("B", vp), ("C", vp), ("bias", vp), ("aux_in", vp), ("aux_out", vp), ("residual", vp),
-        ("a_rowsum", vp),
-        ("M", i64), ("N", i64), ("K", i64),
-        ("lda", i64), ("ldb", i64), ("ldc", i64), ("ld_aux_in", i64), ("ld_aux_out", i64), ("ld_res", i64),
-        ("sAo", i64), ("sAi", i64), ("sBo", i64), ("sBi", i64), ("sCo", i64), ("sCi", i64),
-        ("batch", i32), ("batch_inner", i32), ("a_kmajor", i32), ("b_kmajor", i32),
-        ("in_dtype", i32), ("out_dtype", i32), ("act", i32), ("accumulate", i32), ("split_k", i32),
-        ("alpha", f32), ("dropout_p", f32), ("fp8_fmt", i32), ("dropout_seed", u64),
-        ("scale_a", vp), ("scale_b", vp),
-    ]
+_DECL = re.compile(r"\s*([^;{}]*(?:\{[^{}]*\}[^;{}]*)?);")           # one declaration, with at most one { } block
+_TYPED = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(.*)", re.S)   # base type, stars, the rest
 
 
-class SdpaDesc(C.Structure):
-    """Mirror of favit_sdpa_t (include/favit.h)."""
-    _fields_ = [
-        ("q", vp), ("k", vp), ("v", vp), ("o", vp), ("lse", vp), ("dout", vp), ("dq", vp), ("dk", vp), ("dv", vp),
-        ("delta", vp), ("mask", vp), ("m_sb", i64), ("m_sq", i64),
-        ("q_str", i64 * 3), ("k_str", i64 * 3), ("v_str", i64 * 3), ("o_str", i64 * 3), ("do_str", i64 * 3),
-        ("dq_str", i64 * 3), ("dk_str", i64 * 3), ("dv_str", i64 * 3),
-        ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("hd", i32), ("dtype", i32),
-        ("scale", f32), ("dropout_p", f32), ("seed", u64),
-    ]
+def _refuse(what, decl):
+    raise ValueError(f"favit.h: {what} in `{' '.join(decl.split())}`")
 
 
-class BlockDesc(C.Structure):
-    """Mirror of favit_mhla_block_t (include/favit.h)."""
-    _fields_ = [
-        ("x", vp), ("tape", vp), ("g1", vp), ("b1", vp), ("g2", vp), ("b2", vp), ("weff", vp), ("beff", vp),
-        ("wproj", vp), ("bproj", vp), ("wfc1", vp), ("bfc1", vp), ("wfc2", vp), ("bfc2", vp),
-        ("tape_bytes", i64),
-        ("B", i32), ("n", i32), ("D", i32), ("H", i32), ("W", i32), ("hidden", i32), ("training", i32), ("eps", f32),
-    ]
+def _ctype(base, stars, structs, decl):
+    if not stars:
+        if base not in _SCALARS:
+            _refuse(f"unknown scalar type {base!r}", decl)
+        return _SCALARS[base]
+    return C.POINTER(structs[base]) if base in structs and stars.count("*") == 1 else C.c_void_p
 
 
-class BlockMlp(C.Structure):
-    """Mirror of favit_mhla_block_mlp_t (include/favit.h)."""
-    _fields_ = [("x1c", vp), ("n_mlp", i32), ("reserved", i32)]
+def _struct(name, body, consts, structs, decl):
+    fields = []
+    for line in filter(None, (s.strip() for s in body.split(";"))):
+        typed = _TYPED.fullmatch(line)
+        for item in typed.group(3).split(",") if typed else [""]:
+            m = re.fullmatch(r"\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", item)
+            if not m:
+                _refuse(f"field {line!r} not understood", decl)
+            t = _ctype(typed.group(1), typed.group(2), structs, decl)
+            if m.group(2) is not None:
+                n = int(m.group(2)) if m.group(2).isdigit() else consts.get(m.group(2))
+                if n is None:
+                    _refuse(f"unknown array length {m.group(2)!r}", decl)
+                t = t * n
+            fields.append((m.group(1), t))
+    return type(_STRUCT_NAMES.get(name, name), (C.Structure,),
+                {"_fields_": fields, "__doc__": f"Mirror of {name} (include/favit.h)."})
 
 
-ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN = 64, 256        # FAVIT_ADAMW_MAX_SEGMENTS / _SEG_ALIGN (checked against the library)
+def _prototype(ret, args, structs, decl):
+    ret = re.sub(r"\s*\*", "*", ret)
+    if ret not in _RETURNS:
+        _refuse(f"unknown return type {ret!r}", decl)
+    types = []
+    for arg in ([] if args.strip() == "void" else args.split(",")):
+        m = _TYPED.fullmatch(arg.strip())
+        if not m or not re.fullmatch(r"\w*", m.group(3).strip()):
+            _refuse(f"argument {arg.strip()!r} not understood", decl)
+        types.append(_ctype(m.group(1), m.group(2), structs, decl))
+    return types, _RETURNS[ret]
 
 
-class AdamwMulti(C.Structure):
-    """Mirror of favit_adamw_multi_t (include/favit.h)."""
-    _fields_ = [
-        ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("ema", vp),
-        ("n", i64), ("count", i32), ("skip_nonfinite", i32),
-        ("end", i64 * ADAMW_MAX_SEGMENTS), ("lr", f32 * ADAMW_MAX_SEGMENTS), ("weight_decay", f32 * ADAMW_MAX_SEGMENTS),
-        ("beta1", f32), ("beta2", f32), ("eps", f32), ("bias_c1", f32), ("bias_c2", f32), ("grad_scale", f32),
-        ("ema_decay", f32), ("coef", vp),
-    ]
+def parse_header(text):
+    """(constants {FAVIT_X: int}, structs {favit_x_t: ctypes.Structure}, prototypes {favit_x: (argtypes, restype)})
+    of the text of a header written like include/favit.h; ValueError names the first declaration that is not."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts, structs, sigs = {}, {}, {}
+    for line in re.findall(r"^[ \t]*#[^\n]*", text, flags=re.M):
+        m = re.fullmatch(r"\s*#\s*define\s+(FAVIT_\w+)(?:\s+(-?\d+))?\s*", line)
+        if m and m.group(2) is not None:
+            consts[m.group(1)] = int(m.group(2))
+        elif not m and re.match(r"\s*#\s*define\b", line):
+            _refuse("#define that is no integer constant", line)
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", text)
+    pos = 0
+    while m := _DECL.match(text, pos):
+        pos, decl = m.end(), m.group(1).strip()
+        if e := re.fullmatch(r"enum\s*\{(.*)\}", decl, re.S):
+            for item in filter(None, (s.strip() for s in e.group(1).split(","))):
+                v = re.fullmatch(r"(FAVIT_\w+)\s*=\s*(-?\d+)", item)
+                if not v:
+                    _refuse(f"enumerator {item!r} without an integer value", decl)
+                consts[v.group(1)] = int(v.group(2))
+        elif s := re.fullmatch(r"typedef\s+struct\s+\w*\s*\{(.*)\}\s*(favit_\w+_t)", decl, re.S):
+            structs[s.group(2)] = _struct(s.group(2), s.group(1), consts, structs, decl)
+        elif p := re.fullmatch(r"(.*?)\b(favit_\w+)\s*\((.*)\)", decl, re.S):
+            sigs[p.group(2)] = _prototype(p.group(1).strip(), p.group(3), structs, decl)
+        else:
+            _refuse("declaration not understood", decl)
+    if text[pos:].strip() != "}" * wrapped:
+        _refuse("declaration not understood", text[pos:][:200])
+    return consts, structs, sigs
 
 
-BLOCK_TAPE_SLOTS = ("xn1", "mu1", "rs1", "qkv", "o", "lse", "x1", "xn2", "mu2", "rs2", "h", "pre", "x2")
-BLOCK_BWD_SLOTS = ("dpre", "dxn2", "g1_f32", "g1_lp", "do", "dqkv", "dxn1", "g_out_f32", "g_out_lp", "part1", "part2")
+def _slot_names(prefix, count):
+    """Lower-cased suffixes of the FAVIT_<prefix>* enumerators in value order, which must be 0 .. count - 1."""
+    found = sorted((v, k[len(prefix):].lower()) for k, v in CONSTS.items() if k.startswith(prefix))
+    if [v for v, _ in found] != list(range(count)):
+        raise ValueError(f"favit.h: the {prefix}* enumerators are not 0..{count - 1}")
+    return tuple(k for _, k in found)
 
-_SIGS = {
-    "favit_abi_version": ([], C.c_int),
-    "favit_strerror": ([C.c_int], C.c_char_p),
-    "favit_set_dropout_epoch": ([vp], C.c_int),
-    "favit_set_health_word": ([vp], C.c_int),
-    "favit_gemm": ([C.POINTER(GemmDesc), vp], C.c_int),
-    "favit_gemm_last_kernel": ([], C.c_char_p),
-    "favit_ln_gemm": ([C.POINTER(GemmDesc), vp, i64, vp, vp, f32, vp, vp, vp, vp], C.c_int),
-    "favit_gemm_grouped_tn": ([C.POINTER(GemmDesc), i32, vp], C.c_int),
-    "favit_gemm_grouped_tn_workspace": ([C.POINTER(GemmDesc), i32], C.c_int64),
-    "favit_gemm_grouped_tn_ws": ([C.POINTER(GemmDesc), i32, vp, i64, vp], C.c_int),
-    "favit_gemm_grouped_tn_ragged": ([C.POINTER(GemmDesc), i32, vp], C.c_int),
-    "favit_gemm_grouped_tn_ragged_workspace": ([C.POINTER(GemmDesc), i32], C.c_int64),
-    "favit_gemm_grouped_tn_ragged_ws": ([C.POINTER(GemmDesc), i32, vp, i64, vp], C.c_int),
-    "favit_gemm_grouped_last_splits": ([], C.c_int),
-    "favit_gemm_grouped_plan": ([C.POINTER(GemmDesc), i32, i32, vp, i32], C.c_int),
-    "favit_cast": ([vp, C.c_int, vp, C.c_int, i64, vp], C.c_int),
-    "favit_fp8_amax": ([vp, C.c_int, i64, i64, i64, vp, vp], C.c_int),
-    "favit_fp8_quantize": ([vp, C.c_int, i64, i64, i64, vp, i64, vp, i64, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
-    "favit_layernorm_fwd": ([vp, i64, vp, vp, vp, C.c_int, vp, vp, i64, i32, f32, vp], C.c_int),
-    "favit_layernorm_bwd": ([vp, C.c_int, vp, i64, vp, vp, vp, vp, vp, i64, vp, C.c_int, vp, vp, i32, vp, vp, i32,
-                             i64, i32, f32, u64, vp], C.c_int),
-    "favit_layernorm_fwd_q8": ([vp, i64, vp, vp, vp, vp, vp, i64, i32, f32, vp, C.c_int, vp, vp, vp, vp, vp], C.c_int),
-    "favit_layernorm_bwd_q8": ([vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, i32, i64, i32, f32, u64,
-                                vp, C.c_int, vp, vp, vp, vp, vp], C.c_int),
-    "favit_small_linear_fwd": ([vp, i64, vp, vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_small_linear_bwd": ([vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
-    "favit_reduce_rows": ([vp, i64, vp, i64, i32, i32, vp], C.c_int),
-    "favit_reduce_rows_multi": ([i32, vp, vp, vp, i64, i32, vp], C.c_int),
-    "favit_reduce_rows_multi_ragged": ([i32, vp, vp, vp, vp, i32, vp], C.c_int),
-    "favit_mhla_fold_fwd": ([vp, vp, vp, vp, vp, C.c_int, vp, vp, i32, i32, vp], C.c_int),
-    "favit_mhla_fold_fwd_multi": ([i32, vp, vp, vp, vp, vp, C.c_int, vp, i32, i32, vp], C.c_int),
-    "favit_mhla_fold_bwd": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_mhla_fold_bwd_multi": ([i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp], C.c_int),
-    "favit_mhla_attn_fwd": ([vp, vp, vp, i32, i32, i32, i32, i32, C.c_int, f32, u64, vp], C.c_int),
-    "favit_mhla_attn_bwd": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_int, f32, u64, vp], C.c_int),
-    "favit_mhla_attn_lse_supported": ([i32, i32, i32, C.c_int], C.c_int),
-    "favit_mhla_attn_fwd_lse": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_int, f32, u64, vp], C.c_int),
-    "favit_mhla_attn_bwd_lse": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_int, f32, u64, vp], C.c_int),
-    "favit_sdpa_fwd": ([C.POINTER(SdpaDesc), vp], C.c_int),
-    "favit_sdpa_bwd": ([C.POINTER(SdpaDesc), vp], C.c_int),
-    "favit_softmax_fwd": ([vp, vp, vp, C.c_int, vp, i64, i64, i32, i64, i32, i32, f32, u64, vp], C.c_int),
-    "favit_softmax_bwd": ([vp, C.c_int, vp, vp, C.c_int, i64, i32, i32, f32, u64, vp], C.c_int),
-    "favit_patchify_fwd": ([vp, vp, C.c_int, i32, i32, i32, i32, vp], C.c_int),
-    "favit_patchify_bwd": ([vp, vp, i32, i32, i32, i32, vp], C.c_int),
-    "favit_embed_prologue_fwd": ([vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_embed_prologue_bwd": ([vp, vp, C.c_int, vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_rows_cut_fwd": ([vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
-    "favit_rows_cut_bwd": ([vp, vp, vp, C.c_int, i32, i32, i32, i32, i32, vp], C.c_int),
-    "favit_mhla_block_tape_layout": ([C.POINTER(BlockDesc), C.POINTER(i64)], C.c_int64),
-    "favit_mhla_block_bwd_layout": ([C.POINTER(BlockDesc), i32, C.POINTER(i64)], C.c_int64),
-    "favit_mhla_block_fwd": ([C.POINTER(BlockDesc), vp], C.c_int),
-    "favit_mhla_block_bwd": ([C.POINTER(BlockDesc), vp, vp, vp, i64, i32, vp], C.c_int),
-    "favit_mhla_block_tape_layout2": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), C.POINTER(i64)], C.c_int64),
-    "favit_mhla_block_bwd_layout2": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), i32, C.POINTER(i64)], C.c_int64),
-    "favit_mhla_block_attn_fwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp], C.c_int),
-    "favit_mhla_block_mlp_fwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp], C.c_int),
-    "favit_mhla_block_mlp_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
-    "favit_mhla_block_attn_bwd": ([C.POINTER(BlockDesc), C.POINTER(BlockMlp), vp, vp, vp, i64, i32, vp], C.c_int),
-    "favit_dropout": ([vp, vp, C.c_int, i64, f32, u64, vp], C.c_int),
-    "favit_drop_path_add": ([vp, vp, C.c_int, vp, i32, i32, i32, f32, u64, vp], C.c_int),
-    "favit_drop_path_bwd": ([vp, vp, C.c_int, i32, i32, i32, f32, u64, f32, u64, vp], C.c_int),
-    "favit_sppp_map_patches": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_sppp_pool_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
-    "favit_sppp_pool_bwd": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], C.c_int),
-    "favit_sppp_centroids": ([vp, vp, i32, i32, i32, vp], C.c_int),
-    "favit_sppp_posenc_fwd": ([vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
-    "favit_image_transform": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp], C.c_int),
-    "favit_image_transform_ragged": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp], C.c_int),
-    "favit_slic_features_workspace": ([i32, i32, i32], C.c_int64),
-    "favit_slic_features": ([vp, vp, i32, i32, i32, f32, i32, vp, vp], C.c_int),
-    "favit_slic_cluster_workspace": ([i32, i32], C.c_int64),
-    "favit_slic_cluster": ([vp, vp, vp, i32, i32, i32, i32, i32, i64, i32, vp, vp], C.c_int),
-    "favit_slic_connect": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
-    "favit_cross_entropy": ([vp, vp, vp, vp, i32, i32, f32, vp], C.c_int),
-    "favit_adamw": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp], C.c_int),
-    "favit_cross_entropy_ls": ([vp, vp, vp, vp, i32, i32, f32, f32, vp], C.c_int),
-    "favit_grad_norm_workspace": ([], C.c_int64),
-    "favit_grad_norm": ([i32, vp, vp, f32, f32, vp, vp, vp, i64, vp], C.c_int),
-    "favit_adamw_clip": ([vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, vp], C.c_int),
-    "favit_adamw_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp], C.c_int),
-    "favit_adamw_clip_ema": ([vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp, i32, f32, vp],
-                             C.c_int),
-    "favit_swap_params": ([vp, vp, vp, i64, vp], C.c_int),
-    "favit_adamw_multi": ([C.POINTER(AdamwMulti), vp], C.c_int),
-    "favit_adamw_multi_max_segments": ([], C.c_int),
-    "favit_adamw_multi_align": ([], C.c_int),
-    "favit_batch_mix": ([vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
-    "favit_cross_entropy_mix": ([vp, vp, vp, vp, vp, i32, i32, f32, f32, vp], C.c_int),
-    "favit_randaugment_max_ops": ([], C.c_int),
-    "favit_randaugment": ([vp, vp, vp, vp, vp, i32, vp, C.POINTER(f32), i32, u64, i32, i32, i32, C.POINTER(f32),
-                           C.POINTER(f32), vp], C.c_int),
-    "favit_random_erase": ([vp, vp, C.POINTER(f32), i32, u64, i32, i32, i32, i32, vp], C.c_int),
-    "favit_cross_entropy_distill": ([vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, i32, vp], C.c_int),
-}
+
+with open(HEADER_PATH) as _f:
+    CONSTS, STRUCTS, _SIGS = parse_header(_f.read())      # _SIGS: name -> (argtypes, restype), applied by lib()
+globals().update({k[len("FAVIT_"):]: v for k, v in CONSTS.items()})
+globals().update({_STRUCT_NAMES[k]: v for k, v in STRUCTS.items() if k in _STRUCT_NAMES})
+POOL = {k[len("FAVIT_POOL_"):].lower(): v for k, v in CONSTS.items() if k.startswith("FAVIT_POOL_")}
+# the slot NAMES of the two block layouts, in the order of their offsets (these replace the two counts of the header)
+BLOCK_TAPE_SLOTS = _slot_names("FAVIT_TAPE_", CONSTS["FAVIT_BLOCK_TAPE_SLOTS"])
+BLOCK_BWD_SLOTS = _slot_names("FAVIT_BWD_", CONSTS["FAVIT_BLOCK_BWD_SLOTS"])
 
 _lib = None
 

@@ -42,8 +42,7 @@ __device__ __forceinline__ double mul_rn(double a, double b) { return a * b; }
 __device__ __forceinline__ double add_rn(double a, double b) { return a + b; }
 
 constexpr int AUG_THREADS = 1024;
-constexpr int AUG_MAX_OPS = 8;
-enum { OP_IDENTITY = 0, OP_AFFINE = 1, OP_BLEND = 2, OP_MASK = 3, OP_SOLARIZE = 4, OP_AUTOCONTRAST = 5, OP_EQUALIZE = 6 };
+constexpr int AUG_MAX_OPS = FAVIT_RANDAUGMENT_MAX_OPS;
 
 struct EraseFill {
   float v[3];          // per-channel constant
@@ -96,10 +95,10 @@ __global__ __launch_bounds__(AUG_THREADS) void randaugment_kernel(const uint8_t*
   for (int slot = 0; slot < n_ops; ++slot) {
     const int32_t* row = ops + ((long)b * n_ops + slot) * 8;
     const int op = row[0];
-    if (op < OP_AFFINE || op > OP_EQUALIZE) continue;            // identity: nothing moves
+    if (op < FAVIT_AUG_AFFINE || op > FAVIT_AUG_EQUALIZE) continue;            // identity: nothing moves
     uint8_t* dst = planes + ((long)plane * B + b) * n;
 
-    if (op == OP_AFFINE) {
+    if (op == FAVIT_AUG_AFFINE) {
       const int a0 = row[1], a1 = row[2], a2 = row[3], a3 = row[4], a4 = row[5], a5 = row[6];
       const uint8_t f0 = (uint8_t)(row[7] & 255), f1 = (uint8_t)((row[7] >> 8) & 255), f2 = (uint8_t)((row[7] >> 16) & 255);
       for (int i = tid; i < npix; i += AUG_THREADS) {
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(AUG_THREADS) void randaugment_kernel(const uint8_t*
           o[0] = f0; o[1] = f1; o[2] = f2;
         }
       }
-    } else if (op == OP_BLEND) {
+    } else if (op == FAVIT_AUG_BLEND) {
       const int kind = row[1];
       const float f = __int_as_float(row[2]);
       const bool inside = f >= 0.0f && f <= 1.0f;
@@ -159,18 +158,18 @@ __global__ __launch_bounds__(AUG_THREADS) void randaugment_kernel(const uint8_t*
         }
       }
     } else {                                                       // the LUT ops
-      if (op == OP_MASK || op == OP_SOLARIZE) {
+      if (op == FAVIT_AUG_MASK || op == FAVIT_AUG_SOLARIZE) {
         const int a = row[1];
         for (int i = tid; i < C * 256; i += AUG_THREADS) {
           const int v = i & 255;
-          lut[i >> 8][v] = (uint8_t)(op == OP_MASK ? (v & a) : (v < a ? v : 255 - v));
+          lut[i >> 8][v] = (uint8_t)(op == FAVIT_AUG_MASK ? (v & a) : (v < a ? v : 255 - v));
         }
       } else {
         for (int i = tid; i < C * 256; i += AUG_THREADS) hist[i >> 8][i & 255] = 0;
         __syncthreads();
         for (long i = tid; i < n; i += AUG_THREADS) atomicAdd(&hist[(int)(i % C)][cur[i]], 1);
         __syncthreads();
-        if (op == OP_EQUALIZE) {
+        if (op == FAVIT_AUG_EQUALIZE) {
           // ImageOps.equalize: step = (n - h[last nonzero]) / 255; lut[i] = (step / 2 + sum_{j<i} h[j]) / step, clipped
           if (tid < C) {
             const int c = tid;

@@ -12,8 +12,6 @@
 namespace {
 constexpr int64_t ALIGN = 256;
 constexpr int TAPE_N = FAVIT_BLOCK_TAPE_SLOTS, BWD_N = FAVIT_BLOCK_BWD_SLOTS;
-enum { T_XN1, T_MU1, T_RS1, T_QKV, T_O, T_LSE, T_X1, T_XN2, T_MU2, T_RS2, T_H, T_PRE, T_X2 };
-enum { G_DPRE, G_DXN2, G_G1_F32, G_G1_LP, G_DO, G_DQKV, G_DXN1, G_OUT_F32, G_OUT_LP, G_PART1, G_PART2 };
 
 inline int64_t up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 
@@ -48,13 +46,13 @@ int check_rows(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r) {
 
 void tape_sizes(const favit_mhla_block_t* d, int32_t n_mlp, int64_t* s) {
   const int64_t M = (int64_t)d->B * d->n, Mm = (int64_t)d->B * n_mlp, D = d->D, Hd = d->hidden;
-  s[T_XN1] = M * D * 2; s[T_MU1] = M * 4; s[T_RS1] = M * 4;
-  s[T_QKV] = M * 3 * D * 2; s[T_O] = M * D * 2;
-  s[T_LSE] = d->training ? (int64_t)d->B * d->H * d->n * 4 : 0;
-  s[T_X1] = M * D * 4;
-  s[T_XN2] = Mm * D * 2; s[T_MU2] = Mm * 4; s[T_RS2] = Mm * 4;
-  s[T_H] = Mm * Hd * 2; s[T_PRE] = Mm * Hd * 2;
-  s[T_X2] = Mm * D * 4;
+  s[FAVIT_TAPE_XN1] = M * D * 2; s[FAVIT_TAPE_MU1] = M * 4; s[FAVIT_TAPE_RS1] = M * 4;
+  s[FAVIT_TAPE_QKV] = M * 3 * D * 2; s[FAVIT_TAPE_O] = M * D * 2;
+  s[FAVIT_TAPE_LSE] = d->training ? (int64_t)d->B * d->H * d->n * 4 : 0;
+  s[FAVIT_TAPE_X1] = M * D * 4;
+  s[FAVIT_TAPE_XN2] = Mm * D * 2; s[FAVIT_TAPE_MU2] = Mm * 4; s[FAVIT_TAPE_RS2] = Mm * 4;
+  s[FAVIT_TAPE_H] = Mm * Hd * 2; s[FAVIT_TAPE_PRE] = Mm * Hd * 2;
+  s[FAVIT_TAPE_X2] = Mm * D * 4;
 }
 
 int32_t ln_parts(int64_t rows) { return (int32_t)((rows + 3) / 4 < 2048 ? (rows + 3) / 4 : 2048); }
@@ -62,11 +60,11 @@ int32_t ln_parts(int64_t rows) { return (int32_t)((rows + 3) / 4 < 2048 ? (rows 
 // narrowed (n_mlp < n): g1 leaves the MLP half in fp32 on n_mlp rows; the row cut writes the expanded pair itself
 void bwd_sizes(const favit_mhla_block_t* d, int32_t n_mlp, int want_lp_out, int64_t* s) {
   const int64_t M = (int64_t)d->B * d->n, Mm = (int64_t)d->B * n_mlp, D = d->D, Hd = d->hidden;
-  s[G_DPRE] = Mm * Hd * 2; s[G_DXN2] = Mm * D * 2;
-  s[G_G1_F32] = Mm * D * 4; s[G_G1_LP] = n_mlp == d->n ? M * D * 2 : 0;
-  s[G_DO] = M * D * 2; s[G_DQKV] = M * 3 * D * 2; s[G_DXN1] = M * D * 2;
-  s[G_OUT_F32] = M * D * 4; s[G_OUT_LP] = want_lp_out ? M * D * 2 : 0;
-  s[G_PART1] = 2 * (int64_t)ln_parts(M) * D * 4; s[G_PART2] = 2 * (int64_t)ln_parts(Mm) * D * 4;
+  s[FAVIT_BWD_DPRE] = Mm * Hd * 2; s[FAVIT_BWD_DXN2] = Mm * D * 2;
+  s[FAVIT_BWD_G1_F32] = Mm * D * 4; s[FAVIT_BWD_G1_LP] = n_mlp == d->n ? M * D * 2 : 0;
+  s[FAVIT_BWD_DO] = M * D * 2; s[FAVIT_BWD_DQKV] = M * 3 * D * 2; s[FAVIT_BWD_DXN1] = M * D * 2;
+  s[FAVIT_BWD_G_OUT_F32] = M * D * 4; s[FAVIT_BWD_G_OUT_LP] = want_lp_out ? M * D * 2 : 0;
+  s[FAVIT_BWD_PART1] = 2 * (int64_t)ln_parts(M) * D * 4; s[FAVIT_BWD_PART2] = 2 * (int64_t)ln_parts(Mm) * D * 4;
 }
 
 // a bf16-in GEMM without batch, split or dropout: the fields every GEMM of the two chains shares
@@ -100,19 +98,21 @@ int attn_half_fwd(const favit_mhla_block_t* d, const int64_t* o, void* stream) {
   char* t = reinterpret_cast<char*>(d->tape);
   const int64_t M = (int64_t)d->B * d->n;
   const int32_t D = d->D;
-  if ((rc = favit_layernorm_fwd(d->x, D, d->g1, d->b1, t + o[T_XN1], FAVIT_BF16, reinterpret_cast<float*>(t + o[T_MU1]),
-                                reinterpret_cast<float*>(t + o[T_RS1]), M, D, d->eps, stream)) != FAVIT_OK)
+  if ((rc = favit_layernorm_fwd(d->x, D, d->g1, d->b1, t + o[FAVIT_TAPE_XN1], FAVIT_BF16,
+                                reinterpret_cast<float*>(t + o[FAVIT_TAPE_MU1]),
+                                reinterpret_cast<float*>(t + o[FAVIT_TAPE_RS1]), M, D, d->eps, stream)) != FAVIT_OK)
     return rc;
-  favit_gemm_t g = gemm_base(t + o[T_XN1], d->weff, t + o[T_QKV], M, 3 * D, D, D, 1, FAVIT_BF16);
+  favit_gemm_t g = gemm_base(t + o[FAVIT_TAPE_XN1], d->weff, t + o[FAVIT_TAPE_QKV], M, 3 * D, D, D, 1, FAVIT_BF16);
   g.bias = d->beff;
   g.ld_aux_out = 3 * D; g.ld_res = 3 * D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  rc = d->training ? favit_mhla_attn_fwd_lse(t + o[T_QKV], t + o[T_O], reinterpret_cast<float*>(t + o[T_LSE]), nullptr,
-                                             d->B, d->n, d->H, 64, d->W, FAVIT_BF16, 0.f, 0, stream)
-                   : favit_mhla_attn_fwd(t + o[T_QKV], t + o[T_O], nullptr, d->B, d->n, d->H, 64, d->W, FAVIT_BF16, 0.f, 0,
-                                         stream);
+  rc = d->training ? favit_mhla_attn_fwd_lse(t + o[FAVIT_TAPE_QKV], t + o[FAVIT_TAPE_O],
+                                             reinterpret_cast<float*>(t + o[FAVIT_TAPE_LSE]), nullptr, d->B, d->n, d->H, 64,
+                                             d->W, FAVIT_BF16, 0.f, 0, stream)
+                   : favit_mhla_attn_fwd(t + o[FAVIT_TAPE_QKV], t + o[FAVIT_TAPE_O], nullptr, d->B, d->n, d->H, 64, d->W,
+                                         FAVIT_BF16, 0.f, 0, stream);
   if (rc != FAVIT_OK) return rc;
-  g = gemm_base(t + o[T_O], d->wproj, t + o[T_X1], M, D, D, D, 1, FAVIT_F32);
+  g = gemm_base(t + o[FAVIT_TAPE_O], d->wproj, t + o[FAVIT_TAPE_X1], M, D, D, D, 1, FAVIT_F32);
   g.bias = d->bproj; g.residual = d->x;
   g.ld_aux_out = D; g.ld_res = D;
   return favit_gemm(&g, stream);
@@ -123,14 +123,15 @@ int mlp_half_fwd(const favit_mhla_block_t* d, const float* x1, int64_t Mm, const
   int rc;
   char* t = reinterpret_cast<char*>(d->tape);
   const int32_t D = d->D, Hd = d->hidden;
-  if ((rc = favit_layernorm_fwd(x1, D, d->g2, d->b2, t + o[T_XN2], FAVIT_BF16, reinterpret_cast<float*>(t + o[T_MU2]),
-                                reinterpret_cast<float*>(t + o[T_RS2]), Mm, D, d->eps, stream)) != FAVIT_OK)
+  if ((rc = favit_layernorm_fwd(x1, D, d->g2, d->b2, t + o[FAVIT_TAPE_XN2], FAVIT_BF16,
+                                reinterpret_cast<float*>(t + o[FAVIT_TAPE_MU2]),
+                                reinterpret_cast<float*>(t + o[FAVIT_TAPE_RS2]), Mm, D, d->eps, stream)) != FAVIT_OK)
     return rc;
-  favit_gemm_t g = gemm_base(t + o[T_XN2], d->wfc1, t + o[T_H], Mm, Hd, D, D, 1, FAVIT_BF16);
-  g.bias = d->bfc1; g.act = FAVIT_ACT_GELU_SAVEGRAD; g.aux_out = t + o[T_PRE];
+  favit_gemm_t g = gemm_base(t + o[FAVIT_TAPE_XN2], d->wfc1, t + o[FAVIT_TAPE_H], Mm, Hd, D, D, 1, FAVIT_BF16);
+  g.bias = d->bfc1; g.act = FAVIT_ACT_GELU_SAVEGRAD; g.aux_out = t + o[FAVIT_TAPE_PRE];
   g.ld_aux_out = Hd; g.ld_res = Hd;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  g = gemm_base(t + o[T_H], d->wfc2, t + o[T_X2], Mm, D, Hd, Hd, 1, FAVIT_F32);
+  g = gemm_base(t + o[FAVIT_TAPE_H], d->wfc2, t + o[FAVIT_TAPE_X2], Mm, D, Hd, Hd, 1, FAVIT_F32);
   g.bias = d->bfc2; g.residual = x1;
   g.ld_aux_out = D; g.ld_res = D;
   return favit_gemm(&g, stream);
@@ -142,19 +143,20 @@ int mlp_half_bwd(const favit_mhla_block_t* d, const float* x1, int64_t Mm, const
   int rc;
   char* t = reinterpret_cast<char*>(d->tape);
   const int32_t D = d->D, Hd = d->hidden, np = ln_parts(Mm);
-  float* part2 = reinterpret_cast<float*>(w + b[G_PART2]);
+  float* part2 = reinterpret_cast<float*>(w + b[FAVIT_BWD_PART2]);
   // dpre = (g . W2) * gelu'(pre): dX = dY.W with the weight [N, K] read mn-major
-  favit_gemm_t g = gemm_base(g_lp, d->wfc2, w + b[G_DPRE], Mm, Hd, D, Hd, 0, FAVIT_BF16);
-  g.act = FAVIT_ACT_MULAUX; g.aux_in = t + o[T_PRE]; g.ld_aux_in = Hd;
+  favit_gemm_t g = gemm_base(g_lp, d->wfc2, w + b[FAVIT_BWD_DPRE], Mm, Hd, D, Hd, 0, FAVIT_BF16);
+  g.act = FAVIT_ACT_MULAUX; g.aux_in = t + o[FAVIT_TAPE_PRE]; g.ld_aux_in = Hd;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  g = gemm_base(w + b[G_DPRE], d->wfc1, w + b[G_DXN2], Mm, D, Hd, D, 0, FAVIT_BF16);
+  g = gemm_base(w + b[FAVIT_BWD_DPRE], d->wfc1, w + b[FAVIT_BWD_DXN2], Mm, D, Hd, D, 0, FAVIT_BF16);
   g.ld_aux_in = D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
   // LayerNorm 2 backward: the partial sums stay in part2 (dgamma = NULL: the caller folds them later)
-  return favit_layernorm_bwd(w + b[G_DXN2], FAVIT_BF16, x1, D, d->g2, reinterpret_cast<const float*>(t + o[T_MU2]),
-                             reinterpret_cast<const float*>(t + o[T_RS2]), g_f32, reinterpret_cast<float*>(w + b[G_G1_F32]),
-                             D, g1_lp, FAVIT_BF16, part2, part2 + (int64_t)np * D, np, nullptr, nullptr, 1, Mm, D, 0.f, 0,
-                             stream);
+  return favit_layernorm_bwd(w + b[FAVIT_BWD_DXN2], FAVIT_BF16, x1, D, d->g2,
+                             reinterpret_cast<const float*>(t + o[FAVIT_TAPE_MU2]),
+                             reinterpret_cast<const float*>(t + o[FAVIT_TAPE_RS2]), g_f32,
+                             reinterpret_cast<float*>(w + b[FAVIT_BWD_G1_F32]), D, g1_lp, FAVIT_BF16, part2,
+                             part2 + (int64_t)np * D, np, nullptr, nullptr, 1, Mm, D, 0.f, 0, stream);
 }
 
 // do, attention backward, dxn1, LayerNorm 1 backward on B * n rows
@@ -164,21 +166,23 @@ int attn_half_bwd(const favit_mhla_block_t* d, const float* g1, const void* g1_l
   char* t = reinterpret_cast<char*>(d->tape);
   const int64_t M = (int64_t)d->B * d->n;
   const int32_t D = d->D, np = ln_parts(M);
-  float* part1 = reinterpret_cast<float*>(w + b[G_PART1]);
-  favit_gemm_t g = gemm_base(g1_lp, d->wproj, w + b[G_DO], M, D, D, D, 0, FAVIT_BF16);
+  float* part1 = reinterpret_cast<float*>(w + b[FAVIT_BWD_PART1]);
+  favit_gemm_t g = gemm_base(g1_lp, d->wproj, w + b[FAVIT_BWD_DO], M, D, D, D, 0, FAVIT_BF16);
   g.ld_aux_in = D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  if ((rc = favit_mhla_attn_bwd_lse(t + o[T_QKV], w + b[G_DO], t + o[T_O], reinterpret_cast<const float*>(t + o[T_LSE]),
-                                    w + b[G_DQKV], nullptr, d->B, d->n, d->H, 64, d->W, FAVIT_BF16, 0.f, 0, stream)) !=
-      FAVIT_OK)
+  if ((rc = favit_mhla_attn_bwd_lse(t + o[FAVIT_TAPE_QKV], w + b[FAVIT_BWD_DO], t + o[FAVIT_TAPE_O],
+                                    reinterpret_cast<const float*>(t + o[FAVIT_TAPE_LSE]), w + b[FAVIT_BWD_DQKV], nullptr,
+                                    d->B, d->n, d->H, 64, d->W, FAVIT_BF16, 0.f, 0, stream)) != FAVIT_OK)
     return rc;
-  g = gemm_base(w + b[G_DQKV], d->weff, w + b[G_DXN1], M, D, 3 * D, D, 0, FAVIT_BF16);
+  g = gemm_base(w + b[FAVIT_BWD_DQKV], d->weff, w + b[FAVIT_BWD_DXN1], M, D, 3 * D, D, 0, FAVIT_BF16);
   g.ld_aux_in = D;
   if ((rc = favit_gemm(&g, stream)) != FAVIT_OK) return rc;
-  return favit_layernorm_bwd(w + b[G_DXN1], FAVIT_BF16, d->x, D, d->g1, reinterpret_cast<const float*>(t + o[T_MU1]),
-                             reinterpret_cast<const float*>(t + o[T_RS1]), g1, reinterpret_cast<float*>(w + b[G_OUT_F32]), D,
-                             want_lp_out ? w + b[G_OUT_LP] : nullptr, FAVIT_BF16, part1, part1 + (int64_t)np * D, np, nullptr,
-                             nullptr, 1, M, D, 0.f, 0, stream);
+  return favit_layernorm_bwd(w + b[FAVIT_BWD_DXN1], FAVIT_BF16, d->x, D, d->g1,
+                             reinterpret_cast<const float*>(t + o[FAVIT_TAPE_MU1]),
+                             reinterpret_cast<const float*>(t + o[FAVIT_TAPE_RS1]), g1,
+                             reinterpret_cast<float*>(w + b[FAVIT_BWD_G_OUT_F32]), D,
+                             want_lp_out ? w + b[FAVIT_BWD_G_OUT_LP] : nullptr, FAVIT_BF16, part1, part1 + (int64_t)np * D,
+                             np, nullptr, nullptr, 1, M, D, 0.f, 0, stream);
 }
 
 // what every chain call checks before its first launch; fills the tape offsets
@@ -235,8 +239,8 @@ extern "C" int favit_mhla_block_fwd(const favit_mhla_block_t* d, void* stream) {
   if ((rc = check_call(d, d->n, o)) != FAVIT_OK) return rc;
   // ---- nothing has been launched above this line ----
   if ((rc = attn_half_fwd(d, o, stream)) != FAVIT_OK) return rc;
-  return mlp_half_fwd(d, reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[T_X1]), (int64_t)d->B * d->n, o,
-                      stream);
+  return mlp_half_fwd(d, reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[FAVIT_TAPE_X1]),
+                      (int64_t)d->B * d->n, o, stream);
 }
 
 extern "C" int favit_mhla_block_bwd(const favit_mhla_block_t* d, const float* g_f32, const void* g_lp, void* bwd_buffers,
@@ -247,9 +251,11 @@ extern "C" int favit_mhla_block_bwd(const favit_mhla_block_t* d, const float* g_
   if ((rc = check_bwd_call(d, d->n, g_f32, g_lp, bwd_buffers, bwd_bytes, want_lp_out, o, b)) != FAVIT_OK) return rc;
   // ---- nothing has been launched above this line ----
   char* w = reinterpret_cast<char*>(bwd_buffers);
-  const float* x1 = reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[T_X1]);
-  if ((rc = mlp_half_bwd(d, x1, (int64_t)d->B * d->n, g_f32, g_lp, o, w, b, w + b[G_G1_LP], stream)) != FAVIT_OK) return rc;
-  return attn_half_bwd(d, reinterpret_cast<const float*>(w + b[G_G1_F32]), w + b[G_G1_LP], o, w, b, want_lp_out, stream);
+  const float* x1 = reinterpret_cast<const float*>(reinterpret_cast<char*>(d->tape) + o[FAVIT_TAPE_X1]);
+  if ((rc = mlp_half_bwd(d, x1, (int64_t)d->B * d->n, g_f32, g_lp, o, w, b, w + b[FAVIT_BWD_G1_LP], stream)) != FAVIT_OK)
+    return rc;
+  return attn_half_bwd(d, reinterpret_cast<const float*>(w + b[FAVIT_BWD_G1_F32]), w + b[FAVIT_BWD_G1_LP], o, w, b,
+                       want_lp_out, stream);
 }
 
 // ---- the block in two halves with a row cut between them ----
@@ -306,7 +312,7 @@ extern "C" int favit_mhla_block_mlp_bwd(const favit_mhla_block_t* d, const favit
   // ---- nothing has been launched above this line ----
   char* w = reinterpret_cast<char*>(bwd_buffers);
   return mlp_half_bwd(d, r->x1c, (int64_t)d->B * r->n_mlp, g_f32, g_lp, o, w, b,
-                      r->n_mlp == d->n ? w + b[G_G1_LP] : nullptr, stream);
+                      r->n_mlp == d->n ? w + b[FAVIT_BWD_G1_LP] : nullptr, stream);
 }
 
 extern "C" int favit_mhla_block_attn_bwd(const favit_mhla_block_t* d, const favit_mhla_block_mlp_t* r, const float* g1_f32,

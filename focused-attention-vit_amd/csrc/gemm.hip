@@ -2201,7 +2201,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_s64ln_kernel(KParams p, Ln
 //     grouped_reduce_kernel adds the slabs in split order (deterministic; no fp32 atomics);  a chunk with one split:
 //     the tile epilogue writes dW itself (reading the previous value when the problem accumulates) -- in a ragged
 //     launch the short blocks take this path beside long blocks that are split.
-constexpr int GROUP_MAX = 48;
+constexpr int GROUP_MAX = FAVIT_GEMM_GROUP_MAX;
 constexpr int GROUP_XCD_UNITS = 24;     // units in one XCD's queue, at most
 struct TnProb {          // 64 bytes
   const void* A;         // dY [T, M], mn-major

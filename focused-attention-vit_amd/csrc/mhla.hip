@@ -1912,7 +1912,7 @@ __global__ __launch_bounds__(256) void fold_bwd_all_kernel(const float* __restri
 // The backward folds of up to FOLD_BWD_MAX layers in ONE launch (blockIdx.y = layer): each is ~100 small
 // workgroups and latency-bound (22.9 us x 12 per cfg2 step as separate launches), the gradients they produce
 // (qkv.{weight,bias}, latent_proj.{weight,bias}) feed nothing in the backward chain.  Accumulating form only.
-constexpr int FOLD_BWD_MAX = 16;
+constexpr int FOLD_BWD_MAX = FAVIT_FOLD_BWD_MAX;
 struct FoldBwdBatch {
   const float* dweff[FOLD_BWD_MAX];
   const float* dbeff[FOLD_BWD_MAX];
@@ -1940,7 +1940,7 @@ __global__ __launch_bounds__(256) void fold_bwd_multi_kernel(FoldBwdBatch fb, in
 
 // Forward folds of up to FOLD_MAX independent blocks (the layers of one encoder) in ONE launch:
 // the fold only depends on parameters, so all of them can run before the first block.
-constexpr int FOLD_MAX = 32;
+constexpr int FOLD_MAX = FAVIT_FOLD_MAX;
 struct FoldBatch {
   const float* wqkv[FOLD_MAX];
   const float* bqkv[FOLD_MAX];

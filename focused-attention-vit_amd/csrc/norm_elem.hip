@@ -332,7 +332,7 @@ __global__ __launch_bounds__(1024) void reduce_rows_kernel(const float* __restri
 // Several stacked-pair reductions in ONE launch (the dgamma / dbeta partials of up to REDUCE_MULTI_MAX LayerNorm
 // backward passes: 24 launches of ~5 us per cfg2 step otherwise).  Entry e: in [2][rows][cols] -> out0, out1 [cols],
 // ADDED to the destinations (rows split over gridDim.z / n blocks, fp32 atomics as in the single form).
-constexpr int REDUCE_MULTI_MAX = 32;
+constexpr int REDUCE_MULTI_MAX = FAVIT_REDUCE_ROWS_MULTI_MAX;
 struct ReduceMulti {
   const float* in[REDUCE_MULTI_MAX];
   float* out0[REDUCE_MULTI_MAX];
@@ -890,7 +890,7 @@ __global__ void swap_params_kernel(float* __restrict__ a, float* __restrict__ b,
 // which element in which order depends only on the buffers' addresses and lengths: no atomics, the same bits every
 // run.  Launch 2: one workgroup adds the GRAD_NORM_PARTS partials in a fixed order and writes the two results.
 // ---------------------------------------------------------------------------------
-constexpr int GRAD_NORM_MAX = 16;
+constexpr int GRAD_NORM_MAX = FAVIT_GRAD_NORM_MAX_BUFS;
 constexpr int GRAD_NORM_PARTS = 1024;
 struct GradNormBufs {
   const float* p[GRAD_NORM_MAX];
@@ -1121,7 +1121,7 @@ extern "C" int favit_layernorm_bwd_q8(const void* dy, const float* x, int64_t ld
 // atomics (deterministic), 3-4 us each.
 // ---------------------------------------------------------------------------------
 namespace {
-constexpr int SL_MAX_N = 64;
+constexpr int SL_MAX_N = FAVIT_SMALL_LINEAR_MAX_N;
 
 __global__ __launch_bounds__(256) void small_linear_fwd_kernel(const float* __restrict__ x, long ldx,
                                                                const float* __restrict__ w,

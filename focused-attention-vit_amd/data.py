@@ -429,9 +429,10 @@ class RandAugment:
     OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
            "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
     SIGNED = frozenset(OPS[1:10])
-    MAX_OPS = 8            # csrc/augment.hip: AUG_MAX_OPS (favit_randaugment_max_ops)
+    MAX_OPS = _abi.RANDAUGMENT_MAX_OPS
     # kernel op ids (include/favit.h)
-    K_IDENTITY, K_AFFINE, K_BLEND, K_MASK, K_SOLARIZE, K_AUTOCONTRAST, K_EQUALIZE = range(7)
+    K_IDENTITY, K_AFFINE, K_BLEND, K_MASK = _abi.AUG_IDENTITY, _abi.AUG_AFFINE, _abi.AUG_BLEND, _abi.AUG_MASK
+    K_SOLARIZE, K_AUTOCONTRAST, K_EQUALIZE = _abi.AUG_SOLARIZE, _abi.AUG_AUTOCONTRAST, _abi.AUG_EQUALIZE
     _BLEND_KIND = {"Brightness": 0, "Color": 1, "Contrast": 2, "Sharpness": 3}
 
     def __init__(self, num_ops: int = 2, magnitude: int = 9, num_magnitude_bins: int = 31,

@@ -170,7 +170,7 @@ def ln_gemm(x, ldx, gamma, beta, w, out, M, N, D, *, bias=None, act=ACT_NONE, au
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     rc = _abi.lib().favit_ln_gemm(C.byref(d), _p(x), ldx, _p(gamma), _p(beta), eps, _p(xn), _p(mean), _p(rstd), _st())
-    if rc == -2:
+    if rc == _abi.ERR_UNSUPPORTED:
         return None
     _abi.check(rc, "favit_ln_gemm")
     if GEMM_TRACE is not None:
@@ -188,7 +188,7 @@ _GROUPED_WS = {}          # device index -> workspace tensor of the slab-mode sp
 _GROUPED_WS_RETIRED = []
 
 
-GROUP_MAX = 48            # problems per grouped launch (csrc/gemm.hip)
+GROUP_MAX = _abi.GEMM_GROUP_MAX            # problems per grouped launch (include/favit.h)
 
 
 def gemm_grouped_tn(problems, use_workspace: bool = True) -> bool:
@@ -262,7 +262,7 @@ def _grouped_launch(problems, use_workspace, ragged):
         rc = f_ws(arr, n, _p(ws), ws.numel(), _st())
     else:
         rc = f_plain(arr, n, _st())
-    if rc == -2:
+    if rc == _abi.ERR_UNSUPPORTED:
         return False
     _abi.check(rc, "favit_gemm_grouped_tn")
     if GEMM_TRACE is not None:
@@ -282,7 +282,7 @@ class Fp8History:
     after) and the scale_inv scalar the GEMM reads."""
     __slots__ = ("slots", "scale_inv", "calls")
 
-    NSLOT = 256                                   # FAVIT_FP8_AMAX_SLOTS: partial maxima per array
+    NSLOT = _abi.FP8_AMAX_SLOTS                   # partial maxima per array
 
     def __init__(self, device):
         self.slots = torch.zeros(3 * self.NSLOT, dtype=torch.float32, device=device)
@@ -376,7 +376,7 @@ def layernorm_fwd(x, ldx, gamma, beta, rows, D, out_dtype, eps=1e-5, q8=None):
     return y, mean, rstd
 
 
-SMALL_LINEAR_MAX_N = 64
+SMALL_LINEAR_MAX_N = _abi.SMALL_LINEAR_MAX_N
 
 
 def small_linear_fwd(x, w, bias):
@@ -460,8 +460,8 @@ def reduce_rows_multi(entries):
     differ (one cols) go through reduce_rows_multi_ragged, still one launch."""
     if entries and any(tuple(e[0].shape) != tuple(entries[0][0].shape) for e in entries):
         return reduce_rows_multi_ragged(entries)
-    for i in range(0, len(entries), 32):
-        chunk = entries[i:i + 32]
+    for i in range(0, len(entries), _abi.REDUCE_ROWS_MULTI_MAX):
+        chunk = entries[i:i + _abi.REDUCE_ROWS_MULTI_MAX]
         n = len(chunk)
         rows, cols = chunk[0][0].shape[1], chunk[0][0].shape[2]
         arr = C.c_void_p * n
@@ -485,8 +485,8 @@ def reduce_rows_multi_ragged(entries):
         require_gpu(part, o0, o1)
         if part.dim() != 3 or part.shape[0] != 2 or part.shape[2] != cols or not part.is_contiguous() or part.dtype != torch.float32:
             raise ValueError("reduce_rows_multi: every entry must be a contiguous fp32 [2, rows, cols] stack of one cols")
-    for i in range(0, len(entries), 32):
-        chunk = entries[i:i + 32]
+    for i in range(0, len(entries), _abi.REDUCE_ROWS_MULTI_MAX):
+        chunk = entries[i:i + _abi.REDUCE_ROWS_MULTI_MAX]
         n = len(chunk)
         arr = C.c_void_p * n
         rows = (C.c_int64 * n)(*[e[0].shape[1] for e in chunk])
@@ -553,8 +553,8 @@ def mhla_fold_bwd(dweff, dbeff, wqkv, bqkv, wl, H, out=None):
 def mhla_fold_bwd_multi(entries, H):
     """entries: [(dweff, dbeff, wqkv, bqkv, wl, (dwqkv, dbqkv, dwl, dbl))] of equal geometry: every layer's fold
     backward in ONE launch (chunks of 16), ACCUMULATING into the gradient buffers."""
-    for i in range(0, len(entries), 16):
-        chunk = entries[i:i + 16]
+    for i in range(0, len(entries), _abi.FOLD_BWD_MAX):
+        chunk = entries[i:i + _abi.FOLD_BWD_MAX]
         n = len(chunk)
         D = chunk[0][2].shape[1]
         arr = C.c_void_p * n
@@ -1183,7 +1183,7 @@ def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0, mix_lam=
     return loss_rows, dlog
 
 
-GRAD_NORM_MAX_BUFS = 16
+GRAD_NORM_MAX_BUFS = _abi.GRAD_NORM_MAX_BUFS
 
 
 def grad_norm_workspace(device) -> torch.Tensor:
@@ -1262,20 +1262,16 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_lp=None
                "favit_adamw_clip")
 
 
+ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN = _abi.ADAMW_MAX_SEGMENTS, _abi.ADAMW_SEG_ALIGN
+
+
 def _adamw_limits():
-    """(FAVIT_ADAMW_MAX_SEGMENTS, FAVIT_ADAMW_SEG_ALIGN) as the loaded library reports them."""
+    """(FAVIT_ADAMW_MAX_SEGMENTS, FAVIT_ADAMW_SEG_ALIGN) as the loaded library reports them: a library built from
+    another header than the one _abi read is refused."""
     got = (int(_abi.lib().favit_adamw_multi_max_segments()), int(_abi.lib().favit_adamw_multi_align()))
-    if got != (_abi.ADAMW_MAX_SEGMENTS, _abi.ADAMW_SEG_ALIGN):
+    if got != (ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN):
         raise _abi.FavitLibraryError("libfavit.so and _abi.AdamwMulti disagree on the segment table's size")
     return got
-
-
-def __getattr__(name):
-    """ADAMW_MAX_SEGMENTS / ADAMW_SEG_ALIGN: read from the library at first use, so that importing this module still
-    does not need the library."""
-    if name in ("ADAMW_MAX_SEGMENTS", "ADAMW_SEG_ALIGN"):
-        return _adamw_limits()[name == "ADAMW_SEG_ALIGN"]
-    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def adamw_multi(p, g, m, v, ends, lrs, wds, beta1, beta2, eps, step, grad_scale=1.0, p_lp=None, coef=None,
@@ -1285,7 +1281,7 @@ def adamw_multi(p, g, m, v, ends, lrs, wds, beta1, beta2, eps, step, grad_scale=
     is updated with lrs[s] and wds[s]; everything else is shared.  Per element the bits are adamw()'s on the segment's
     slice.  The table is a by-value argument of the launch: plain Python numbers, read at every call.  coef,
     skip_nonfinite, ema, ema_decay: as in adamw().  ValueError for a table the library would refuse."""
-    ADAMW_MAX_SEGMENTS, ADAMW_SEG_ALIGN = _adamw_limits()
+    _adamw_limits()
     ends, lrs, wds = [int(e) for e in ends], [float(x) for x in lrs], [float(x) for x in wds]
     require_gpu(p, g, m, v, p_lp, ema, coef)
     for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):

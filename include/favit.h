@@ -18,6 +18,10 @@
  *     fp32 accumulation, bf16 MFMA) / FAVIT_FP8 (GEMM operands only: OCP e4m3 / e5m2 bytes
  *     with per-tensor scales, fp32 accumulation, fp8 MFMA)
  *   - kernels are stateless and thread-compatible
+ *   - focused-attention-vit_amd/_abi.py READS this file and derives the whole ctypes binding from it, so keep its form:
+ *     constants as `#define FAVIT_X <integer>` or enumerators with explicit values, structs as
+ *     `typedef struct tag { ... } favit_x_t;` with array lengths that are literals or FAVIT_* constants, prototypes
+ *     with the scalar types int, int32_t, int64_t, uint32_t, uint64_t and float.  Anything else fails the import.
  */
 #ifndef FAVIT_H_
 #define FAVIT_H_
@@ -160,6 +164,7 @@ int favit_ln_gemm(const favit_gemm_t* g, const float* x, int64_t ldx, const floa
  * than a_rowsum (bias gradient, always ADDED to its destination) and accumulate; returns
  * FAVIT_ERR_UNSUPPORTED otherwise (the caller then issues them one by one).  The number of K-splits is
  * chosen by a cost model (v7): with enough tiles in the launch it is 1, and then no workspace is used. */
+#define FAVIT_GEMM_GROUP_MAX 48   /* problems per grouped launch, plain or ragged */
 int favit_gemm_grouped_tn(const favit_gemm_t* gs, int32_t count, void* stream);
 /* The same launch with a caller-provided device workspace of favit_gemm_grouped_tn_workspace(gs, count) bytes:
  * every K-split writes its partial results to a slab of the workspace with plain stores and a second kernel adds
@@ -255,6 +260,7 @@ int favit_layernorm_bwd_q8(const void* dy, const float* x, int64_t ldx, const fl
  * (accumulate = 1 adds to dw / db).  N <= 64 (FAVIT_ERR_UNSUPPORTED beyond: those heads are GEMMs); no atomics.
  * Reference: nn.Linear(embed_dim, num_classes) on the normalised CLS row, models/vit.py:259,306,
  * models/vit_mhla.py:156,249, models/sppp_mhla.py:240,318. */
+#define FAVIT_SMALL_LINEAR_MAX_N 64
 int favit_small_linear_fwd(const float* x, int64_t ldx, const float* w, const float* bias, float* y, int32_t M, int32_t N,
                            int32_t K, void* stream);
 int favit_small_linear_bwd(const float* dy, const float* x, int64_t ldx, const float* w, float* dx, float* dw, float* db,
@@ -262,6 +268,7 @@ int favit_small_linear_bwd(const float* dy, const float* x, int64_t ldx, const f
 /* out[c] (+)= sum_r in[r*ld + c] */
 int favit_reduce_rows(const float* in, int64_t ld, float* out, int64_t rows, int32_t cols, int32_t accumulate,
                       void* stream);
+#define FAVIT_REDUCE_ROWS_MULTI_MAX 32   /* entries per favit_reduce_rows_multi / _multi_ragged launch */
 /* n (<= 32) stacked-pair reductions in ONE launch: entry e adds the column sums of in[e] ([2][rows][cols], contiguous)
  * to out0[e] / out1[e] ([cols] each).  Used for the dgamma / dbeta partials of several favit_layernorm_bwd calls
  * (each called with dgamma = NULL): the arguments are HOST arrays of n device pointers. */
@@ -283,6 +290,8 @@ int favit_mhla_fold_fwd(const float* wqkv, const float* bqkv, const float* wl, c
                         int weff_dtype, float* weff_f32 /* optional fp32 copy */, float* beff, int32_t D,
                         int32_t H, void* stream);
 /* accumulate=1: the four outputs are added to (gradient buffers), else overwritten */
+#define FAVIT_FOLD_MAX 32       /* blocks per favit_mhla_fold_fwd_multi launch */
+#define FAVIT_FOLD_BWD_MAX 16   /* layers per favit_mhla_fold_bwd_multi launch */
 /* The forward fold of n (<= 32) independent blocks -- e.g. every layer of an encoder -- in ONE launch.
  * The arguments are HOST arrays of n device pointers; weff[i] / beff[i] as in favit_mhla_fold_fwd. */
 int favit_mhla_fold_fwd_multi(int32_t n, const float* const* wqkv, const float* const* bqkv, const float* const* wl,
@@ -485,6 +494,16 @@ int favit_rows_cut_bwd(const float* dy, float* dx, void* dx_lp, int lp_dtype, in
  * ---------------------------------------------------------------------------------- */
 #define FAVIT_BLOCK_TAPE_SLOTS 13
 #define FAVIT_BLOCK_BWD_SLOTS 11
+enum {   /* index of every tape slot in offsets_out */
+  FAVIT_TAPE_XN1 = 0, FAVIT_TAPE_MU1 = 1, FAVIT_TAPE_RS1 = 2, FAVIT_TAPE_QKV = 3, FAVIT_TAPE_O = 4, FAVIT_TAPE_LSE = 5,
+  FAVIT_TAPE_X1 = 6, FAVIT_TAPE_XN2 = 7, FAVIT_TAPE_MU2 = 8, FAVIT_TAPE_RS2 = 9, FAVIT_TAPE_H = 10, FAVIT_TAPE_PRE = 11,
+  FAVIT_TAPE_X2 = 12
+};
+enum {   /* index of every slot of the backward's allocation in offsets_out */
+  FAVIT_BWD_DPRE = 0, FAVIT_BWD_DXN2 = 1, FAVIT_BWD_G1_F32 = 2, FAVIT_BWD_G1_LP = 3, FAVIT_BWD_DO = 4,
+  FAVIT_BWD_DQKV = 5, FAVIT_BWD_DXN1 = 6, FAVIT_BWD_G_OUT_F32 = 7, FAVIT_BWD_G_OUT_LP = 8, FAVIT_BWD_PART1 = 9,
+  FAVIT_BWD_PART2 = 10
+};
 typedef struct favit_mhla_block {
   const float* x;       /* block input: fp32 [B*n, D], the residual stream */
   void* tape;           /* tape_bytes >= the tape layout's size */
@@ -614,6 +633,7 @@ int favit_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, int6
 int favit_cross_entropy_ls(const float* logits, const int64_t* labels, float* loss_rows, float* dlogits, int32_t B,
                            int32_t C, float grad_scale, float label_smoothing, void* stream);
 
+#define FAVIT_GRAD_NORM_MAX_BUFS 16
 /* Global L2 norm of n (0..16) flat fp32 buffers, bufs[i] / lens[i] (host arrays, copied by value into the launch):
  * any 4-byte-aligned address, any length >= 0 (a NULL buffer needs length 0).
  *   out[0] = scale * sqrt(sum_i sum_j bufs[i][j]^2)      (scale: AdamW's grad_scale, 1 / world)
@@ -741,6 +761,11 @@ int favit_cross_entropy_mix(const float* logits, const int64_t* labels, const fl
  *     draws 2 idx and 2 idx + 1 of the library's counter-based generator under erase_seed, idx = ((b*C + c)*S + y)*S + x
  *     (a function of the seed and the element alone).
  * An all-identity table without erase_box gives the bits of favit_image_transform's out. */
+#define FAVIT_RANDAUGMENT_MAX_OPS 8
+enum {   /* the op ids of the table above */
+  FAVIT_AUG_IDENTITY = 0, FAVIT_AUG_AFFINE = 1, FAVIT_AUG_BLEND = 2, FAVIT_AUG_MASK = 3, FAVIT_AUG_SOLARIZE = 4,
+  FAVIT_AUG_AUTOCONTRAST = 5, FAVIT_AUG_EQUALIZE = 6
+};
 int favit_randaugment_max_ops(void);
 int favit_randaugment(const uint8_t* src_u8, uint8_t* scratch, float* out, uint8_t* out_u8, const int32_t* ops,
                       int32_t n_ops, const int32_t* erase_box, const float* erase_value, int32_t erase_normal,
