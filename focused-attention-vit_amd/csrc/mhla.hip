@@ -310,13 +310,16 @@ __device__ __forceinline__ void row_softmax(const Slice<T, DPL>& q, const char* 
     p[w] = s;
     m = fmaxf(m, s);
   }
+  // every window key masked: m = -inf.  exp(-inf - 0) = 0 for every slot, l = 0, and the row's probabilities are 0
+  // (output 0, no gradient: the contract of include/favit.h), not exp(-inf + inf) = NaN
+  if (m == -INFINITY) m = 0.f;
   float l = 0.f;
 #pragma unroll
   for (int w = 0; w < WMAX; ++w) {
     p[w] = (w < a.W) ? __expf(p[w] - m) : 0.f;
     l += p[w];
   }
-  const float inv = 1.0f / l;
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
 #pragma unroll
   for (int w = 0; w < WMAX; ++w) p[w] *= inv;
 }
@@ -690,7 +693,8 @@ __global__ __launch_bounds__(256) void mhla_fwd_mfma_kernel(AttnArgs a) {
     lsum = fmaf(mult[e], sc[e], lsum);
   }
   lsum = quad16_sum(lsum);
-  const float inv_l = 1.0f / lsum;
+  // (masked: a row with every window key masked has lsum = 0: its probabilities are 0 and its lse = -inf + log 0 = -inf)
+  const float inv_l = (PLAIN || lsum > 0.f) ? 1.0f / lsum : 0.f;
   if (a.lse_out && g == 0 && qvalid) a.lse_out[((long)b * a.H + head) * L + i] = mx + __logf(lsum);
   bf16x8 pf;
 #pragma unroll
@@ -1144,7 +1148,9 @@ __global__ __launch_bounds__(256) void mhla_bwd_mfma2_kernel(AttnArgs a) {
       lsum = fmaf(mult[e], sc[e], lsum);
     }
     lsum = quad16_sum(lsum);
-    const float inv_l = 1.0f / lsum;
+    // (masked: every window key of the row masked -> lsum = 0: probabilities 0, delta 0, lse = -inf, so that pass 2
+    // adds nothing of this row to dK / dV)
+    const float inv_l = (PLAIN || lsum > 0.f) ? 1.0f / lsum : 0.f;
     float dot = 0.f;
     float dpn[8];
 #pragma unroll

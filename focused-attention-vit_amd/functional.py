@@ -354,6 +354,16 @@ def _mask_u8(mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return (mask != 0).to(torch.uint8).contiguous()
 
 
+def _check_mask_shape(who: str, mask: Optional[torch.Tensor], form: str, shape) -> None:
+    """An attention chain's mask must have the module's documented form: the kernels index it with those extents, so
+    another rank or extent (a [B, L] key-keep mask handed to an MHLA module, say) would be read past its end."""
+    if mask is None:
+        return
+    if not torch.is_tensor(mask) or tuple(mask.shape) != tuple(shape):
+        got = tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__
+        raise ValueError(f"{who}: the attention mask must be {form} = {tuple(shape)}, got {got}")
+
+
 # ------------------------------------------------------------------------------------
 # GEMM helpers (nn.Linear forward / backward)
 # ------------------------------------------------------------------------------------
@@ -739,7 +749,8 @@ class MHLAChain:
 
     def fwd(self, xn, prm, B, L, residual, mask, training, pre=None, ln=None):
         """ln = (x, gamma, beta, out): the LayerNorm in front of this branch is fused into the qkv projection (xn is
-        None); out receives (xn, mean, rstd)."""
+        None); out receives (xn, mean, rstd).  mask: [B, L, L] (0 = masked) or None."""
+        _check_mask_shape("MHLAChain", mask, "[B, L, L]", (B, L, L))
         wqkv, bqkv, wl, bl, wp, bp = prm
         M, D = xn.shape if ln is None else ln[0].shape
         cdt = xn.dtype if ln is None else get_compute_dtype()
@@ -830,6 +841,7 @@ class DenseChain:
         return (_View(t, 0, ld, L * ld, hd), _View(t, D, ld, L * ld, hd), _View(t, 2 * D, ld, L * ld, hd))
 
     def fwd(self, xn, prm, B, L, residual, mask, training, ln=None):
+        _check_mask_shape("DenseChain", mask, "key-keep [B, L]", (B, L))
         wqkv, bqkv, wp, bp = prm
         M, D = xn.shape if ln is None else ln[0].shape
         H, hd = self.H, D // self.H
@@ -882,6 +894,7 @@ class CrossChain:
         self.H, self.p_attn = H, p_attn
 
     def fwd(self, qn, kn, prm, B, Lq, Lk, residual, mask, training):
+        _check_mask_shape("CrossChain", mask, "[B, Lq, Lk]", (B, Lq, Lk))
         wq, bq, wk, bk, wv, bv, wo, bo = prm
         D = qn.shape[1]
         H, hd = self.H, D // self.H

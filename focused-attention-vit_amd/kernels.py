@@ -574,9 +574,39 @@ def mhla_attn_lse_supported(L, hd, W, dtype) -> bool:
     return code is not None and bool(_abi.lib().favit_mhla_attn_lse_supported(L, hd, W, code))
 
 
+def _check_mhla_mask(mask, qkv, B, L):
+    """The kernels index mask[(b*L + i)*L + j] as bytes: anything but a contiguous uint8 / bool [B, L, L] on the inputs'
+    device would be read out of bounds, or as the bytes of another type."""
+    if mask is None:
+        return
+    ok = (torch.is_tensor(mask) and mask.dtype in (torch.uint8, torch.bool) and tuple(mask.shape) == (B, L, L)
+          and mask.is_contiguous() and mask.device == qkv.device)
+    if not ok:
+        got = (f"{mask.dtype} {tuple(mask.shape)} on {mask.device}, {'' if mask.is_contiguous() else 'not '}contiguous"
+               if torch.is_tensor(mask) else type(mask).__name__)
+        raise ValueError(f"MHLA attention mask: expected a contiguous uint8 or bool tensor of shape ({B}, {L}, {L}) on "
+                         f"{qkv.device}, got {got}")
+
+
+def _check_dense_mask(what, mask, m_sb, m_sq, B, Lq, Lk):
+    """The dense kernels read mask[b*m_sb + q*m_sq + k] as bytes, for b < B, q < Lq, k < Lk."""
+    if mask is None:
+        return
+    need = (B - 1) * m_sb + (Lq - 1) * m_sq + Lk
+    ok = (torch.is_tensor(mask) and mask.dtype in (torch.uint8, torch.bool) and mask.is_contiguous() and m_sb >= 0
+          and m_sq >= 0 and mask.numel() >= need)
+    if not ok:
+        got = (f"{mask.dtype} {tuple(mask.shape)} ({mask.numel()} elements), {'' if mask.is_contiguous() else 'not '}"
+               f"contiguous" if torch.is_tensor(mask) else type(mask).__name__)
+        raise ValueError(f"{what} mask: expected a contiguous uint8 or bool tensor of at least {need} elements "
+                         f"(B = {B}, Lq = {Lq}, Lk = {Lk}, batch stride {m_sb}, query stride {m_sq}), got {got}")
+
+
 def mhla_attn_fwd(qkv, B, L, H, hd, W, mask=None, p=0.0, seed=0, want_lse=False):
     """Attention core; with want_lse returns (out, lse fp32 [B, H, L]) -- lse is None where the saved-statistics
-    backward does not apply (the caller then uses mhla_attn_bwd without it)."""
+    backward does not apply (the caller then uses mhla_attn_bwd without it).  mask: contiguous uint8 / bool [B, L, L]
+    (non-zero = keep) or None; a row with every window key masked gives out = 0 and lse = -inf (include/favit.h)."""
+    _check_mhla_mask(mask, qkv, B, L)
     require_gpu(qkv, mask)
     out = torch.empty((B * L, H * hd), dtype=qkv.dtype, device=qkv.device)
     if want_lse and mhla_attn_lse_supported(L, hd, W, qkv.dtype):
@@ -591,6 +621,7 @@ def mhla_attn_fwd(qkv, B, L, H, hd, W, mask=None, p=0.0, seed=0, want_lse=False)
 
 def mhla_attn_bwd(qkv, dout, B, L, H, hd, W, mask=None, p=0.0, seed=0, o=None, lse=None):
     """dqkv of the attention core; with the forward's output and lse the saved-statistics kernel runs."""
+    _check_mhla_mask(mask, qkv, B, L)
     require_gpu(qkv, dout, mask, o, lse)
     dqkv = torch.empty_like(qkv)
     if o is not None and lse is not None:
@@ -740,6 +771,7 @@ def _sdpa_desc(q, k, v, o, lse, B, H, Lq, Lk, hd, scale, mask, m_sb, m_sq, p, se
 
 def sdpa_fwd(q, k, v, o, B, H, Lq, Lk, hd, scale, mask=None, m_sb=0, m_sq=0, p=0.0, seed=0):
     """Fused attention forward: writes o (view) and returns lse [B*H, Lq] fp32 (saved for backward)."""
+    _check_dense_mask("favit_sdpa_fwd", mask, m_sb, m_sq, B, Lq, Lk)
     require_gpu(q.t, k.t, v.t, o.t, mask)
     lse = torch.empty((B * H, Lq), dtype=torch.float32, device=q.t.device)
     d = _sdpa_desc(q, k, v, o, lse, B, H, Lq, Lk, hd, scale, mask, m_sb, m_sq, p, seed)
@@ -749,6 +781,7 @@ def sdpa_fwd(q, k, v, o, B, H, Lq, Lk, hd, scale, mask=None, m_sb=0, m_sq=0, p=0
 
 def sdpa_bwd(q, k, v, o, do, dq, dk, dv, lse, B, H, Lq, Lk, hd, scale, mask=None, m_sb=0, m_sq=0, p=0.0, seed=0):
     """Fused attention backward: writes dq, dk, dv (views); probabilities are recomputed from lse."""
+    _check_dense_mask("favit_sdpa_bwd", mask, m_sb, m_sq, B, Lq, Lk)
     require_gpu(q.t, k.t, v.t, o.t, do.t, dq.t, dk.t, dv.t, lse, mask)
     delta = torch.empty((B * H, Lq), dtype=torch.float32, device=q.t.device)
     d = _sdpa_desc(q, k, v, o, lse, B, H, Lq, Lk, hd, scale, mask, m_sb, m_sq, p, seed)
@@ -761,6 +794,7 @@ def sdpa_bwd(q, k, v, o, do, dq, dk, dv, lse, B, H, Lq, Lk, hd, scale, mask=None
 
 
 def softmax_fwd(S, p_dtype, H, Z, Lq, Lk, mask=None, m_sb=0, m_sq=0, p=0.0, seed=0):
+    _check_dense_mask("favit_softmax_fwd", mask, m_sb, m_sq, (Z - 1) // H + 1, Lq, Lk)     # mask batch of row z: z / H
     require_gpu(S, mask)
     P = torch.empty((Z, Lq, Lk), dtype=p_dtype, device=S.device)
     Pd = torch.empty_like(P) if p > 0 else None

@@ -314,7 +314,14 @@ int favit_mhla_fold_bwd_multi(int32_t n, const float* const* dweff, const float*
  * scores / sqrt(hd) (130-133), optional mask[B,L,L]!=0 keep (136-143), softmax + dropout
  * (146-147), attn.V (151-154), head merge (157).  qkv is the [B*L, 3D] output of the folded
  * projection (column = s*D + h*hd + d); out is [B*L, D] (column = h*hd + d).
- * Backward recomputes the probabilities and writes dqkv [B*L, 3D]. */
+ * Backward recomputes the probabilities and writes dqkv [B*L, 3D].
+ * mask: one byte per (b, query, key), any non-zero byte keeps the key; NULL = no mask.
+ * A query row whose window keys are ALL masked (PyTorch's softmax gives NaN there; ordinary with a padding mask
+ * mask[b, :, j] = j < n_b: the rows n_b + W/2 <= i < L - W/2, the last W/2 rows keep the pad copies of key 0 in
+ * their windows) follows the contract of favit_sdpa_fwd below: its row of out is 0
+ * (and its lse, where the forward leaves one, is -inf), and in bwd it gets dq = 0 and adds nothing to dk or dv.  No
+ * other row is affected and nothing non-finite is written.  A masked slot of a live row has P = 0 exactly.  This
+ * holds for both pairs of entry points below, in every dtype, head size and kernel selection. */
 int favit_mhla_attn_fwd(const void* qkv, void* out, const uint8_t* mask, int32_t B, int32_t L, int32_t H,
                         int32_t hd, int32_t W, int dtype, float dropout_p, uint64_t seed, void* stream);
 int favit_mhla_attn_bwd(const void* qkv, const void* dout, void* dqkv, const uint8_t* mask, int32_t B, int32_t L,
@@ -325,7 +332,9 @@ int favit_mhla_attn_bwd(const void* qkv, const void* dout, void* dqkv, const uin
  * backward recomputes no softmax for rows outside a workgroup's block (P = exp(s - lse); delta = dO . O for the halo
  * rows: o is in bf16, so delta of those rows carries its rounding, ~2^-9 relative) -- the cfg2 launch takes 66 us
  * against 79.  favit_mhla_attn_lse_supported: 1 where both entry points run (bf16, hd = 64, odd W <= 7, or <= 11 with
- * L > 16; L >= W + 1), else the callers use the pair above. */
+ * L > 16; L >= W + 1), else the callers use the pair above.
+ * A query row whose window keys are all masked (contract above): fwd writes o = 0 and lse = -inf for it, and bwd,
+ * given that pair, gives it dq = 0 and adds nothing to dk or dv (P = 0 on every slot, delta = dO . 0 = 0). */
 int favit_mhla_attn_lse_supported(int32_t L, int32_t hd, int32_t W, int dtype);
 int favit_mhla_attn_fwd_lse(const void* qkv, void* out, float* lse, const uint8_t* mask, int32_t B, int32_t L, int32_t H,
                             int32_t hd, int32_t W, int dtype, float dropout_p, uint64_t seed, void* stream);

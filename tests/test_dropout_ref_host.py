@@ -155,3 +155,188 @@ def test_sdpa_ref_fully_masked_row_is_zero_and_gives_no_gradient():
     o2, _, dq2, dk2, dv2 = R.sdpa_ref(q[1:, :, sel], k[1:], v[1:], dout[1:, :, sel], 0.5, mask[1:, :, sel], None, 0.0)
     assert rel_l2(o[1:, :, sel], o2) < 1e-12 and rel_l2(dq[1:, :, sel], dq2) < 1e-12
     assert rel_l2(dk[1:], dk2) < 1e-12 and rel_l2(dv[1:], dv2) < 1e-12
+
+
+# --------------------------------------------------------------------------------------
+# Masked window attention: dead rows, the structured mask families, the module reference
+# --------------------------------------------------------------------------------------
+def _mhla_core_plain(q, k, v, W, mask):
+    """mhla_core as it was before it learnt about dead rows: plain masked_fill + torch.softmax."""
+    B, H, L, hd = q.shape
+    idx = torch.from_numpy(O.window_indices(L, W))
+    kw, vw = k[:, :, idx], v[:, :, idx]
+    s = (q.unsqueeze(3) @ kw.transpose(-2, -1)).squeeze(3) / (hd ** 0.5)
+    if mask is not None:
+        wm = torch.gather(mask[:, None].expand(B, H, L, L), 3, idx[None, None].expand(B, H, L, W))
+        s = s.masked_fill(wm == 0, float("-inf"))
+    P = torch.softmax(s, -1)
+    return (P.unsqueeze(3) @ vw).squeeze(3), torch.logsumexp(s.detach(), -1)
+
+
+def _core_run(fn, t, dout, W, mask):
+    t = t.detach().clone().requires_grad_(True)
+    o, lse = fn(t[0], t[1], t[2], W, mask)
+    o.backward(dout)
+    return o.detach(), lse, t.grad
+
+
+MASK_SHAPES = [(5, 7, 16), (17, 5, 32), (40, 15, 16), (12, 7, 64), (70, 7, 64), (40, 11, 64), (33, 9, 128), (49, 7, 64)]
+MB, MH = 2, 2
+
+
+@pytest.mark.parametrize("L,W,hd", [(5, 3, 16), (5, 7, 16), (17, 5, 32), (40, 15, 16), (33, 9, 8), (70, 7, 64)])
+def test_mhla_core_without_dead_rows_is_bit_identical_to_plain_softmax(L, W, hd):
+    g = torch.Generator().manual_seed(L * 31 + W)
+    t = torch.randn(3, MB, 3, L, hd, generator=g, dtype=torch.float64)
+    dout = torch.randn(MB, 3, L, hd, generator=g, dtype=torch.float64)
+    mask = _mask(MB, L, g)
+    assert not bool(R.mhla_dead_rows(mask, L, W).any())
+    for m in (None, mask):
+        old, new = _core_run(_mhla_core_plain, t, dout, W, m), _core_run(lambda *a: R.mhla_core(*a), t, dout, W, m)
+        assert all(torch.equal(a, b) for a, b in zip(old, new))
+
+
+@pytest.mark.parametrize("L,W,hd", [(5, 7, 16), (17, 5, 32), (70, 7, 64)])
+def test_mhla_core_dead_rows_are_zero_and_touch_no_other_row(L, W, hd):
+    """out = 0, lse = -inf, dq = 0 on a dead row, nothing non-finite; dk and dv are those of the same problem with the
+    dead rows alive (their diagonal kept) and their output gradient zero: such a row has dS = 0 and P dO = 0 too."""
+    g = torch.Generator().manual_seed(L + W)
+    t = torch.randn(3, MB, MH, L, hd, generator=g, dtype=torch.float64)
+    dout = torch.randn(MB, MH, L, hd, generator=g, dtype=torch.float64)
+    mask = R.mask_family("rows", MB, L, W, g)
+    dead = R.mhla_dead_rows(mask, L, W)
+    assert int(dead.sum()) == R.mask_family_dead_count("rows", MB, L, W) > 0
+    o, lse, grad = _core_run(lambda *a: R.mhla_core(*a), t, dout, W, R.mask_to_u8("rows", mask, g))
+    assert all(bool(torch.isfinite(x).all()) for x in (o, grad))
+    dh = dead[:, None].expand(MB, MH, L)
+    assert bool((o[dh] == 0).all()) and bool((grad[0][dh] == 0).all()) and bool((lse[dh] == float("-inf")).all())
+    assert bool(torch.isfinite(lse[~dh]).all())
+    alive = mask | (torch.eye(L, dtype=torch.bool)[None] & dead[:, :, None])
+    o2, lse2, grad2 = _core_run(lambda *a: R.mhla_core(*a), t, dout * (~dh)[..., None], W, alive)
+    assert torch.equal(o[~dh], o2[~dh]) and torch.equal(lse[~dh], lse2[~dh])
+    assert rel_l2(grad, grad2) < 1e-14
+
+
+@pytest.mark.parametrize("name", R.MASK_FAMILIES)
+@pytest.mark.parametrize("L,W,hd", MASK_SHAPES + [(8, 7, 64), (17, 7, 64), (40, 7, 16), (40, 3, 32)])
+def test_mask_family_dead_row_counts(L, W, hd, name):
+    """Every family has the dead rows its closed form says, at every shape the GPU tests use."""
+    g = torch.Generator().manual_seed(L * 31 + W)
+    mask = R.mask_family(name, MB, L, W, g)
+    assert mask.shape == (MB, L, L) and mask.dtype == torch.bool
+    dead = R.mhla_dead_rows(mask, L, W)
+    assert int(dead.sum()) == R.mask_family_dead_count(name, MB, L, W), name
+    h = W // 2
+    if name in ("rows", "image"):
+        assert bool(dead.any())
+    if name == "rows":
+        assert {tuple(r) for r in dead.nonzero().tolist()} == set(R.rows_family_dead(MB, L))
+        u8 = R.mask_to_u8(name, mask, g)
+        assert torch.equal(u8 != 0, mask) and set(u8.unique().tolist()) <= {0, 1, 2, 255}
+        assert L < 8 or {1, 2, 255} <= set(u8.unique().tolist())
+    if name == "padding" and L > W:      # the last h rows live through the front pad copies of key 0 alone
+        assert not bool(dead[:, L - h:].any()) and bool(dead[1, 1 + h:L - h].all())
+        assert not bool(mask[1, L - 1, 1:].any())
+    if name == "ends" and L > W + 1:
+        assert bool(dead[:, h + 1:L - 1 - h].all()) and not bool(dead[:, :h + 1].any()) and not bool(dead[:, L - 1 - h:].any())
+
+
+@pytest.mark.parametrize("L,W,hd", MASK_SHAPES)
+def test_identity_mask_gives_out_v_and_no_score_gradient(L, W, hd):
+    g = torch.Generator().manual_seed(L)
+    D = MH * hd
+    qkv = torch.randn(MB * L, 3 * D, generator=g, dtype=torch.float64)
+    dout = torch.randn(MB * L, D, generator=g, dtype=torch.float64)
+    mask = R.mask_family("identity", MB, L, W, g)
+    out, dqkv, lse = R.mhla_ref(qkv, dout, MB, L, MH, hd, W, mask, None, 0.0)
+    assert torch.equal(out, qkv[:, 2 * D:]) and torch.equal(dqkv[:, 2 * D:], dout)
+    assert bool((dqkv[:, :2 * D] == 0).all()) and bool(torch.isfinite(lse).all())
+    gross = R.mhla_grad_scale(qkv, dout, MB, L, MH, hd, W, mask, None, 0.0)
+    assert bool((gross[:, :2 * D] > 0).all()) and bool((gross[:, 2 * D:] == 0).all())
+
+
+def _attn_sd(D, hd, g):
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    return {"qkv.weight": r(3 * D, D) / D ** 0.5, "qkv.bias": 0.1 * r(3 * D), "latent_proj.weight": r(hd, hd) / hd ** 0.5,
+            "latent_proj.bias": 0.1 * r(hd), "proj.weight": r(D, D) / D ** 0.5, "proj.bias": 0.1 * r(D)}
+
+
+@pytest.mark.parametrize("L,W,hd", [(5, 7, 16), (17, 5, 32), (40, 15, 16), (70, 7, 64)])
+def test_mhla_attention_ref_equals_the_oracle_without_dead_rows(L, W, hd):
+    g = torch.Generator().manual_seed(L * 3 + W)
+    D = MH * hd
+    sd = _attn_sd(D, hd, g)
+    x = torch.randn(MB, L, D, generator=g, dtype=torch.float64)
+    for mask in (None, _mask(MB, L, g), R.mask_family("identity", MB, L, W, g).to(torch.uint8)):
+        assert rel_l2(R.mhla_attention_ref(x, sd, "", MH, W, mask), O.mhla_attention(x, sd, "", MH, W, mask)) < 1e-12
+
+
+def test_mhla_attention_ref_equals_the_oracle_on_the_golden_masks():
+    from conftest import case, load_golden, sd_of
+    z = load_golden("mhla.npz")
+    names = sorted({k.split("/")[0] for k in z.files if k.startswith("attn_mask")})
+    assert names
+    for name in names:
+        c = case(z, name)
+        W = int(name.split("_W")[1])
+        sd = {k: v.double() for k, v in sd_of(c).items()}
+        x, mask = torch.from_numpy(c["in0"]).double(), torch.from_numpy(c["attention_mask"])
+        assert not bool(R.mhla_dead_rows(mask, x.shape[1], W).any())
+        assert rel_l2(R.mhla_attention_ref(x, sd, "", 4, W, mask), O.mhla_attention(x, sd, "", 4, W, mask)) < 1e-12
+
+
+def test_mhla_attention_ref_dead_row_output_is_the_projection_bias():
+    L, W, hd = 40, 7, 64
+    g = torch.Generator().manual_seed(11)
+    D = MH * hd
+    sd = {k: v.requires_grad_(True) for k, v in _attn_sd(D, hd, g).items()}
+    x = torch.randn(MB, L, D, generator=g, dtype=torch.float64, requires_grad=True)
+    for name in ("rows", "padding"):
+        mask = R.mask_family(name, MB, L, W, g)
+        dead = R.mhla_dead_rows(mask, L, W)
+        assert bool(dead.any())
+        y = R.mhla_attention_ref(x, sd, "", MH, W, mask.to(torch.uint8))
+        assert torch.equal(y[dead], sd["proj.bias"].detach().expand(int(dead.sum()), D))
+        grads = torch.autograd.grad((y * torch.randn(y.shape, generator=g, dtype=torch.float64)).sum(), [x] + list(sd.values()))
+        assert all(bool(torch.isfinite(t).all()) for t in grads)
+        assert bool(torch.isnan(O.mhla_attention(x, sd, "", MH, W, mask.to(torch.uint8))[dead]).all()), "the oracle's softmax gives NaN there"
+
+
+def test_float32_reference_meets_the_fp32_row_gate_with_the_gross_denominator(capsys):
+    """The per-row gate of the fp32 kernels (2.9e-6, tests/test_gpu_dropout_masks.py) against |ref row| is not met on
+    the structured masks even by this reference run in plain float32: rows with one or two surviving keys cancel in dq
+    and dk.  Against the gross-term rows of mhla_grad_scale the float32 run stays an order of magnitude below the gate
+    on all five families, so tests/test_gpu_mhla_masks.py measures dq and dk rows against them.  Figures are printed."""
+    worst = {"out": 0.0, "dv": 0.0, "dq gross": 0.0, "dk gross": 0.0, "dq |ref row|": 0.0, "dk |ref row|": 0.0}
+    where = {}
+    for L, W, hd in MASK_SHAPES:
+        D = MH * hd
+        for name in R.MASK_FAMILIES:
+            g = torch.Generator().manual_seed(L * 31 + W * 7 + hd)
+            qkv = torch.randn(MB * L, 3 * D, generator=g)
+            dout = torch.randn(MB * L, D, generator=g)
+            mask = R.mask_to_u8(name, R.mask_family(name, MB, L, W, g), g)
+            for p in (0.0, 0.25):
+                keep = R.mhla_keep(5, MB, MH, L, W, p) if p > 0 else None
+                o64, g64, _ = R.mhla_ref(qkv, dout, MB, L, MH, hd, W, mask, keep, p)
+                gross = R.mhla_grad_scale(qkv, dout, MB, L, MH, hd, W, mask, keep, p)
+                t = qkv.reshape(MB, L, 3, MH, hd).permute(2, 0, 3, 1, 4).clone().requires_grad_(True)
+                o, _ = R.mhla_core(t[0], t[1], t[2], W, mask, keep, p)
+                o32 = o.transpose(1, 2).reshape(MB * L, D)
+                o32.backward(dout)
+                g32 = t.grad.permute(1, 3, 0, 2, 4).reshape(MB * L, 3 * D)
+                assert o32.dtype == torch.float32 and g32.dtype == torch.float32
+                part = lambda x, s: x[:, s * D:(s + 1) * D]
+                figs = {"out": R.row_error(o32, o64, o64, MB * L), "dv": R.row_error(part(g32, 2), part(g64, 2), part(g64, 2), MB * L),
+                        "dq gross": R.row_error(part(g32, 0), part(g64, 0), part(gross, 0), MB * L),
+                        "dk gross": R.row_error(part(g32, 1), part(g64, 1), part(gross, 1), MB * L),
+                        "dq |ref row|": R.row_error(part(g32, 0), part(g64, 0), part(g64, 0), MB * L),
+                        "dk |ref row|": R.row_error(part(g32, 1), part(g64, 1), part(g64, 1), MB * L)}
+                for k, e in figs.items():
+                    if e.max().item() > worst[k]:
+                        worst[k], where[k] = e.max().item(), f"{name} L={L} W={W} hd={hd} p={p}"
+    with capsys.disabled():
+        for k, e in worst.items():
+            print(f"\n[mhla masks, float32 reference] worst row {k}: {e:.3e} ({where.get(k)})", end="")
+    for k in ("out", "dv", "dq gross", "dk gross"):
+        assert worst[k] < 2.9e-6, f"{k}: {worst[k]:.3e} at {where[k]}"
