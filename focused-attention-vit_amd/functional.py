@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import os
 import weakref
+from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -446,30 +447,6 @@ def lin_fwd(a, w_c, bias, M, N, Kd, out_dtype, *, act=ACT_NONE, residual=None, w
     return (out, pre) if want_pre else out
 
 
-# LayerNorm fused into the qkv / fc1 projections at short token counts (favit_ln_gemm).  OFF by default: built, at
-# parity (tests/test_gpu_kernels.py::test_layernorm_fused_into_small_gemm) and measured at no gain -- cfg3 2.53 ms
-# fused vs 2.48 separate, cfg1 1.90 vs 1.92, cfg5 2.13 vs 2.07: the normalisation is a serial latency chain (load the
-# rows, two reductions, normalise, write the LDS panel) in front of the first MFMA of every workgroup, about as long as
-# the 4.9-us launch it replaces, and it is repeated by the 9-12 column tiles of a row block.  FAVIT_LN_FUSE=1 enables it.
-_LN_FUSE = bool(os.environ.get("FAVIT_LN_FUSE"))
-
-
-def lin_fwd_ln(ln, w_c, bias, M, N, Kd, out_dtype, *, act=ACT_NONE, want_pre=False, drop=(0.0, 0)):
-    """lin_fwd whose A operand is LayerNorm(x): one launch at short token counts (favit_ln_gemm), else layernorm_fwd +
-    lin_fwd.  ln = (x fp32 [M, Kd], gamma, beta).  Returns (out, pre or None, xn, mean, rstd)."""
-    x, gamma, beta = ln
-    if _LN_FUSE and w_c.dtype == torch.bfloat16 and get_compute_mode() != "fp8":
-        out = torch.empty((M, N), dtype=out_dtype, device=x.device)
-        pre = torch.empty((M, N), dtype=out_dtype, device=x.device) if want_pre else None
-        r = K.ln_gemm(x, Kd, gamma, beta, w_c, out, M, N, Kd, bias=bias, act=act, aux_out=pre, dropout_p=drop[0],
-                      dropout_seed=drop[1])
-        if r is not None:
-            return (out, pre) + r
-    xn, mu, rs = K.layernorm_fwd(x, Kd, gamma, beta, M, Kd, get_compute_dtype())
-    o = lin_fwd(xn, w_c, bias, M, N, Kd, out_dtype, act=act, want_pre=want_pre, drop=drop)
-    return (o + (xn, mu, rs)) if want_pre else (o, None, xn, mu, rs)
-
-
 def lin_bwd_x(dy, w_c, M, N, Kd, out_dtype, *, dgelu_pre=None, pre_is_grad=False, drop=(0.0, 0), allow_fp8=True,
               site=None):
     """dx[M,K] = dy[M,N] @ w[N,K]  (optionally * gelu'(pre) * dropout-mask; pre_is_grad: `dgelu_pre` already holds
@@ -501,25 +478,33 @@ def lin_bwd_x(dy, w_c, M, N, Kd, out_dtype, *, dgelu_pre=None, pre_is_grad=False
 # A pruned (CLS-only) encoder has a different token count in every block.  Until round 8 a grouped launch shared one
 # token count and such an encoder launched per block; favit_gemm_grouped_tn_ragged plans K-splits per block, so its
 # blocks join one list under the same limits ("ragged").  The blocks grow as backward walks down (5 .. 71 rows at cfg2),
-# so the list is launched BEFORE the next block would pass a limit: EncoderOp.bwd tells flush_wgrads how many rows the
+# so the list is launched BEFORE the next block would pass a limit: EncoderOp.bwd tells end_block how many rows the
 # next block has.  "ends" are the list lengths at the block boundaries: if the library declines a ragged list, it is
 # launched block by block as before (then GEMM by GEMM), never half of it.
-_WG = {"list": None, "blocks": 0, "every": 1, "bytes": 0, "ragged": False, "ends": [], "blk_bytes": 0}
 _WG_HOLD_BYTES = int(float(os.environ.get("FAVIT_WGRAD_HOLD_MB", "384")) * (1 << 20))
 # (ragged lists wait longer by default: the pruned cfg2 encoder holds 1.4 GB in all and its step is fastest with ONE
 # launch for the twelve blocks -- DESIGN.md section 11 has the A/B; FAVIT_WGRAD_HOLD_MB sets both limits)
 _WG_HOLD_RAGGED_BYTES = int(float(os.environ.get("FAVIT_WGRAD_HOLD_MB", "2048")) * (1 << 20))
 
 
-def begin_wgrads(per_block: bool = False) -> None:
-    """per_block: the token count differs from block to block (CLS-only encoders).  The blocks are grouped through the
-    ragged launch; in side-stream mode and with FAVIT_WGRAD_PER_BLOCK set every block launches on its own."""
-    every = 4 if _STATE["grad_ready"] is not None else K.GROUP_MAX // 4
-    ragged = per_block
-    if _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
-        every = 1                             # (side-stream mode and the A/B switch: one launch per block, as in round 3)
-        ragged = False
-    _WG.update(list=[], blocks=0, every=every, bytes=0, ragged=ragged, ends=[], blk_bytes=0)
+# Small latency-bound launches that only produce PARAMETER gradients (nothing downstream in the backward chain reads
+# them) are collected per encoder backward and issued batched: the latent_proj fold backward (one ~100-workgroup launch
+# per layer: 22.9 us x 12 per cfg2 step) and the fold of the LayerNorm dgamma / dbeta partial sums (one per LayerNorm
+# backward: 4.7 us x 24).  Single process: one batch at the end of the encoder backward; under data parallelism whenever
+# the grouped weight-gradient launch has gone out (every 4 blocks), so that the buckets holding these gradients start
+# their all-reduce while the rest of backward still runs.  The fold consumes dWeff: never before that launch.
+#
+# Zero-initialised fp32 vectors for fused column sums that have no gradient buffer to accumulate into (the bias
+# gradient of the folded qkv weights, one per block): carved out of ONE zero-filled pool per encoder backward instead
+# of one 5-us fill launch each (12 per cfg2 step).
+
+# What waits in a _BackwardQueue, as named records:
+# a weight-gradient GEMM, dw (+)= dy^T a with db += column sums of dy; ready: the parameters to announce afterwards
+_WGrad = namedtuple("_WGrad", "dy a dw db accumulate ready")
+# a latent_proj fold backward (K.mhla_fold_bwd_multi); out: the four gradient buffers, None where a half is switched off
+_Fold = namedtuple("_Fold", "dweff dbeff wqkv bqkv wl out H ready")
+# a fold of LayerNorm partial sums into the dgamma / dbeta buffers (K.reduce_rows_multi)
+_LNFold = namedtuple("_LNFold", "part dg db ready")
 
 
 def _launch_wgrads(probs) -> None:
@@ -529,37 +514,83 @@ def _launch_wgrads(probs) -> None:
                    a_kmajor=False, b_kmajor=False, a_rowsum=db, accumulate=acc)
 
 
-def flush_wgrads(force: bool = True, next_rows=None) -> bool:
-    """Launch the collected weight-gradient GEMMs (grouped if the library can, else one by one).  force=False: called
-    at the end of a block -- launches only every `every` blocks or once the waiting operands exceed the hold limit.
-    next_rows = (rows of the block that just ended, rows of the next one) where the blocks differ (ragged lists).
-    Returns True if the list is empty afterwards."""
-    lst = _WG["list"]
-    if lst is None:
-        return True
-    if not force:
-        _WG["blocks"] += 1
-        nb = _WG["blocks"]
-        if _WG["ragged"]:
-            ends = _WG["ends"]
-            n_blk = len(lst) - (ends[-1] if ends else 0)
-            b_blk = _WG["bytes"] - _WG["blk_bytes"]
-            ends.append(len(lst))
-            _WG["blk_bytes"] = _WG["bytes"]
+class _BackwardQueue:
+    """What one encoder backward holds back: ``with _BackwardQueue(...) as q`` makes q the current queue (_QUEUE), and
+    lin_bwd_w, MHLAChain.qkv_grads and _zero_vec then queue into it / carve from it instead of launching.  Leaving
+    the ``with`` launches what still waits (weight gradients, then the deferred folds) and joins the side stream; an
+    exception drops everything unlaunched.  Outside a ``with`` _QUEUE is None and everything launches at once.
+    per_block: the token count differs from block to block (CLS-only encoders).  The blocks are grouped through the
+    ragged launch; in side-stream mode and with FAVIT_WGRAD_PER_BLOCK set every block launches on its own (and in
+    side-stream mode nothing is deferred).  zero_floats: size of the zero pool on `device`."""
+
+    def __init__(self, per_block: bool = False, zero_floats: int = 0, device=None):
+        self.every = 4 if _STATE["grad_ready"] is not None else K.GROUP_MAX // 4
+        self.ragged = per_block
+        if _SIDE["enabled"] or os.environ.get("FAVIT_WGRAD_PER_BLOCK"):
+            self.every = 1                    # (side-stream mode and the A/B switch: one launch per block, as in round 3)
+            self.ragged = False
+        self.wgrads: List[_WGrad] = []
+        self.blocks, self.bytes, self.ends, self.blk_bytes = 0, 0, [], 0
+        self.defer = not _SIDE["enabled"]
+        self.folds: List[_Fold] = []
+        self.ln_folds: List[_LNFold] = []
+        self.zeros = torch.zeros(zero_floats, dtype=torch.float32, device=device) if zero_floats > 0 else None
+        self.zero_off = 0
+
+    def __enter__(self):
+        global _QUEUE
+        _QUEUE = self
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        global _QUEUE
+        try:
+            if exc_type is None:
+                self.flush_wgrads()
+                self.flush_deferred()
+        finally:
+            _QUEUE = None
+        if exc_type is None:
+            join_side_stream()
+        else:
+            _SIDE["pending"].clear()          # (the half-collected gradients of the failed backward are dropped)
+        return False
+
+    def add_wgrad(self, dy, a, dw, db, accumulate, ready) -> None:
+        self.wgrads.append(_WGrad(dy, a, dw, db, accumulate, ready))
+        self.bytes += dy.numel() * dy.element_size() + a.numel() * a.element_size()
+
+    def end_block(self, next_rows=None) -> bool:
+        """The end of a block: launches the weight gradients only every `every` blocks or once the waiting operands
+        exceed the hold limit.  next_rows = (rows of the block that just ended, rows of the next one) where the blocks
+        differ (ragged lists).  Returns True if no weight gradient waits afterwards."""
+        lst = self.wgrads
+        self.blocks += 1
+        nb = self.blocks
+        if self.ragged:
+            n_blk = len(lst) - (self.ends[-1] if self.ends else 0)
+            b_blk = self.bytes - self.blk_bytes
+            self.ends.append(len(lst))
+            self.blk_bytes = self.bytes
             # (would the NEXT block still fit the hold limit and the launch?  its operands scale with its rows)
             scale = next_rows[1] / max(next_rows[0], 1) if next_rows else 1.0
-            if nb < _WG["every"] and _WG["bytes"] + b_blk * scale <= _WG_HOLD_RAGGED_BYTES and len(lst) + n_blk <= K.GROUP_MAX:
+            if nb < self.every and self.bytes + b_blk * scale <= _WG_HOLD_RAGGED_BYTES and len(lst) + n_blk <= K.GROUP_MAX:
                 return not lst
         # (would one more block of the same size still fit the hold limit and the launch?)
-        elif nb < _WG["every"] and _WG["bytes"] * (nb + 1) <= _WG_HOLD_BYTES * nb and len(lst) * (nb + 1) <= K.GROUP_MAX * nb:
+        elif nb < self.every and self.bytes * (nb + 1) <= _WG_HOLD_BYTES * nb and len(lst) * (nb + 1) <= K.GROUP_MAX * nb:
             return not lst
-    ends = _WG["ends"]
-    _WG.update(blocks=0, bytes=0, ends=[], blk_bytes=0)
-    if lst:
-        _WG["list"] = []
-        probs = [(dy, a, dw, db, acc) for dy, a, dw, db, acc, _ in lst]
-        with _side_stream(*[t for pr in probs for t in pr[:4]]):
-            if not _WG["ragged"]:
+        self.flush_wgrads()
+        return True
+
+    def flush_wgrads(self) -> None:
+        """Launch the collected weight-gradient GEMMs (grouped if the library can, else one by one)."""
+        lst, ends = self.wgrads, self.ends
+        self.wgrads, self.blocks, self.bytes, self.ends, self.blk_bytes = [], 0, 0, [], 0
+        if not lst:
+            return
+        probs = [(e.dy, e.a, e.dw, e.db, e.accumulate) for e in lst]
+        with _side_stream(*[t for e in lst for t in (e.dy, e.a, e.dw, e.db)]):
+            if not self.ragged:
                 _launch_wgrads(probs)
             elif not K.gemm_grouped_tn_ragged(probs):
                 # declined as a whole (a token count that is no multiple of 32): block by block, as before round 8
@@ -567,82 +598,47 @@ def flush_wgrads(force: bool = True, next_rows=None) -> bool:
                 for lo, hi in zip(bounds[:-1], bounds[1:]):
                     if hi > lo:
                         _launch_wgrads(probs[lo:hi])
-            for *_, ready in lst:
-                _ready(*ready)
-    return True
+            for e in lst:
+                _ready(*e.ready)
+
+    def flush_deferred(self) -> None:
+        if not self.defer:
+            return
+        assert not self.wgrads, "the latent_proj fold reads weight gradients that have not been launched"
+        folds, ln = self.folds, self.ln_folds
+        self.folds, self.ln_folds = [], []
+        if ln:
+            by_cols = {}                      # (one launch per width: the row counts of a pruned encoder's blocks differ,
+            for e in ln:                      #  and favit_reduce_rows_multi_ragged takes them together)
+                by_cols.setdefault(e.part.shape[-1], []).append(e)
+            for es in by_cols.values():
+                K.reduce_rows_multi([(e.part, e.dg, e.db) for e in es])
+            for e in ln:
+                _ready(*e.ready)
+        by_h = {}
+        for e in folds:
+            by_h.setdefault((e.H, tuple(e.wqkv.shape), e.out[0] is None), []).append(e)
+        for (H, _, _), es in by_h.items():
+            K.mhla_fold_bwd_multi([(e.dweff, e.dbeff, e.wqkv, e.bqkv, e.wl, e.out) for e in es], H)
+            for e in es:
+                _ready(*e.ready)
+
+    def zero_vec(self, n: int, device) -> torch.Tensor:
+        """n zeros carved from the pool; fresh ones where it is exhausted or lives on another device."""
+        buf = self.zeros
+        n4 = (n + 3) // 4 * 4                 # keep every slice 16-byte aligned (slab reduction)
+        if buf is not None and buf.device == device and self.zero_off + n4 <= buf.numel():
+            o = self.zero_off
+            self.zero_off = o + n4
+            return buf[o:o + n]
+        return torch.zeros(n, dtype=torch.float32, device=device)
 
 
-def end_wgrads() -> None:
-    flush_wgrads()
-    _WG["list"] = None
-
-
-# Small latency-bound launches that only produce PARAMETER gradients (nothing downstream in the backward chain reads
-# them) are collected per encoder backward and issued batched: the latent_proj fold backward (one ~100-workgroup launch
-# per layer: 22.9 us x 12 per cfg2 step) and the fold of the LayerNorm dgamma / dbeta partial sums (one per LayerNorm
-# backward: 4.7 us x 24).  Flushed every `every` blocks, so that under data parallelism the buckets that hold these
-# gradients are still reduced while the rest of backward runs, and at the end of the encoder backward.
-_DEFER = {"on": False, "fold": [], "ln": []}
-
-
-def begin_deferred() -> None:
-    # single process: one batch at the end of the encoder backward; under data parallelism whenever the grouped
-    # weight-gradient launch has gone out (every 4 blocks), so that the buckets holding these gradients start their
-    # all-reduce while the rest of backward still runs.  The fold consumes dWeff: never before that launch.
-    _DEFER.update(on=not _SIDE["enabled"], fold=[], ln=[])
-
-
-def flush_deferred() -> None:
-    if not _DEFER["on"]:
-        return
-    assert not _WG["list"], "the latent_proj fold reads weight gradients that have not been launched"
-    fold, ln = _DEFER["fold"], _DEFER["ln"]
-    _DEFER["fold"], _DEFER["ln"] = [], []
-    if ln:
-        by_cols = {}                          # (one launch per width: the row counts of a pruned encoder's blocks differ,
-        for e in ln:                          #  and favit_reduce_rows_multi_ragged takes them together)
-            by_cols.setdefault(e[0].shape[-1], []).append(e)
-        for es in by_cols.values():
-            K.reduce_rows_multi([e[:3] for e in es])
-        for e in ln:
-            _ready(*e[3])
-    by_h = {}
-    for e in fold:
-        by_h.setdefault((e[6], tuple(e[2].shape), e[5][0] is None), []).append(e)
-    for (H, _, _), es in by_h.items():
-        K.mhla_fold_bwd_multi([e[:6] for e in es], H)
-        for e in es:
-            _ready(*e[7])
-
-
-def end_deferred() -> None:
-    flush_deferred()
-    _DEFER["on"] = False
-
-
-# Zero-initialised fp32 vectors for fused column sums that have no gradient buffer to accumulate into (the bias
-# gradient of the folded qkv weights, one per block): carved out of ONE zero-filled pool per encoder backward instead
-# of one 5-us fill launch each (12 per cfg2 step).
-_ZPOOL = {"buf": None, "off": 0}
-
-
-def begin_zero_pool(n_floats: int, device) -> None:
-    _ZPOOL["buf"] = torch.zeros(n_floats, dtype=torch.float32, device=device) if n_floats > 0 else None
-    _ZPOOL["off"] = 0
-
-
-def end_zero_pool() -> None:
-    _ZPOOL["buf"] = None
+_QUEUE: Optional[_BackwardQueue] = None       # the encoder backward that is running, if any
 
 
 def _zero_vec(n: int, device) -> torch.Tensor:
-    buf = _ZPOOL["buf"]
-    n4 = (n + 3) // 4 * 4                               # keep every slice 16-byte aligned (slab reduction)
-    if buf is not None and buf.device == device and _ZPOOL["off"] + n4 <= buf.numel():
-        o = _ZPOOL["off"]
-        _ZPOOL["off"] = o + n4
-        return buf[o:o + n]
-    return torch.zeros(n, dtype=torch.float32, device=device)
+    return _QUEUE.zero_vec(n, device) if _QUEUE is not None else torch.zeros(n, dtype=torch.float32, device=device)
 
 
 def lin_bwd_w(dy, a, M, N, Kd, want_bias=True, wp=None, bp=None, allow_fp8=True):
@@ -659,11 +655,9 @@ def lin_bwd_w(dy, a, M, N, Kd, want_bias=True, wp=None, bp=None, allow_fp8=True)
     db = None
     if want_bias:
         db = tb if tb is not None else _zero_vec(N, dy.device)
-    if _WG["list"] is not None and dy.dtype == torch.bfloat16:
+    if _QUEUE is not None and dy.dtype == torch.bfloat16:
         # deferred: joins the block's grouped weight-gradient launch
-        _WG["list"].append((dy, a, dw, db, tw is not None,
-                            [p for p, t in ((wp, tw), (bp, tb)) if t is not None]))
-        _WG["bytes"] += dy.numel() * dy.element_size() + a.numel() * a.element_size()
+        _QUEUE.add_wgrad(dy, a, dw, db, tw is not None, [p for p, t in ((wp, tw), (bp, tb)) if t is not None])
         return (None if tw is not None else dw), (None if tb is not None else db)
     with _side_stream(dy, a, dw, db):
         # a long-token weight gradient outside a block (patch embedding: 50,176 tokens at cfg2): the grouped launch
@@ -736,7 +730,22 @@ def sdpa_bwd(q: _View, k: _View, v: _View, o: _View, do: _View, dq: _View, dk: _
 # attention chains: input = LayerNorm output xn [M, D] (compute dtype), output fp32 [M, D]
 # (+ residual fused into the projection epilogue).  bwd takes the compute-dtype copy of the
 # output gradient and returns (dxn [M,D] compute dtype, [param grads in `names` order]).
+# What a chain's fwd saves for its bwd is a record, read by field name everywhere.  Dropout: p_* is the rate in force
+# (0.0 in eval mode), seed_* its seed (0 where the rate is 0).  prm: the chain's parameters in `names` order.
 # ------------------------------------------------------------------------------------
+# xn: the chain's input [M, D]; weff: the qkv weight with latent_proj folded in; qkv [M, 3D]; o: the attention output
+# [M, D]; wp_c: the proj weight in the compute dtype; lse: the row statistics of the saved-statistics backward, or None
+MHLASaved = namedtuple("MHLASaved", "xn weff qkv o wp_c mask B L p_attn seed_attn p_proj seed_proj prm lse")
+# att: what sdpa_fwd saved
+DenseSaved = namedtuple("DenseSaved", "xn wqkv_c qkv o wp_c att mask B L p_attn seed_attn p_proj seed_proj prm")
+# qn / kn: the normalised query / key-value inputs; q, k, v: their projections; w_c: the (q, k, v, out) projection
+# weights in the compute dtype
+CrossSaved = namedtuple("CrossSaved", "qn kn q k v o w_c att mask B Lq Lk p_attn seed_attn scale prm")
+# pre: the fc1 pre-activation, or GELU'(pre) where pre_is_grad; h: fc1's output behind GELU and dropout [M, hidden];
+# p: the one rate of both dropouts (behind fc1 and behind fc2)
+MLPSaved = namedtuple("MLPSaved", "xn pre pre_is_grad h w1_c w2_c p seed_fc1 seed_fc2 prm")
+
+
 class MHLAChain:
     q8_fwd, q8_bwd = 0, 4        # prm index of the weight whose GEMM consumes the chain's input (qkv) / output gradient (proj)
     """MultiHeadLatentAttention.forward (models/mhla.py:85-161)."""
@@ -747,47 +756,44 @@ class MHLAChain:
             raise ValueError("window_size must be odd: the reference crashes on even sizes (models/mhla.py:83)")
         self.H, self.W, self.p_attn, self.p_proj = H, W, p_attn, p_proj
 
-    def fwd(self, xn, prm, B, L, residual, mask, training, pre=None, ln=None):
-        """ln = (x, gamma, beta, out): the LayerNorm in front of this branch is fused into the qkv projection (xn is
-        None); out receives (xn, mean, rstd).  mask: [B, L, L] (0 = masked) or None."""
+    def fwd(self, xn, prm, B, L, residual, mask, training, pre=None):
+        """mask: [B, L, L] (0 = masked) or None.  pre: (weff, beff) where the caller has folded latent_proj already."""
         _check_mask_shape("MHLAChain", mask, "[B, L, L]", (B, L, L))
         wqkv, bqkv, wl, bl, wp, bp = prm
-        M, D = xn.shape if ln is None else ln[0].shape
-        cdt = xn.dtype if ln is None else get_compute_dtype()
+        M, D = xn.shape
         H, hd = self.H, D // self.H
         pa = self.p_attn if training else 0.0
         pp = self.p_proj if training else 0.0
         sa = _seed() if pa > 0 else 0
         sp = _seed() if pp > 0 else 0
-        weff, beff = pre if pre is not None else K.mhla_fold_fwd(wqkv, bqkv, wl, bl, H, cdt)
-        if ln is not None:
-            qkv, _, xn, mu, rs = lin_fwd_ln(ln[:3], weff, beff, M, 3 * D, D, cdt)
-            ln[3][:] = [xn, mu, rs]
-        else:
-            qkv = lin_fwd(xn, weff, beff, M, 3 * D, D, xn.dtype, site=wqkv)
+        weff, beff = pre if pre is not None else K.mhla_fold_fwd(wqkv, bqkv, wl, bl, H, xn.dtype)
+        qkv = lin_fwd(xn, weff, beff, M, 3 * D, D, xn.dtype, site=wqkv)
         # training: the forward also leaves lse per row, and backward runs the saved-statistics kernel (None where
         # that kernel does not apply: other head sizes, fp32)
         o, lse = K.mhla_attn_fwd(qkv, B, L, H, hd, self.W, mask, pa, sa, want_lse=True) if training else \
             (K.mhla_attn_fwd(qkv, B, L, H, hd, self.W, mask, pa, sa), None)
         wp_c = wcast(wp)
         y = lin_fwd(o, wp_c, bp.detach(), M, D, D, torch.float32, residual=residual, drop=(pp, sp), site=wp)
-        return y, (xn, weff, qkv, o, wp_c, mask, B, L, pa, sa, pp, sp, prm, lse)
+        return y, MHLASaved(xn=xn, weff=weff, qkv=qkv, o=o, wp_c=wp_c, mask=mask, B=B, L=L, p_attn=pa, seed_attn=sa,
+                            p_proj=pp, seed_proj=sp, prm=prm, lse=lse)
 
     @staticmethod
     def out_dropout(saved):
         """(p, seed) of the dropout on this branch's output (the mask its incoming gradient must carry)."""
-        return saved[10], saved[11]
+        return saved.p_proj, saved.seed_proj
 
     def bwd(self, saved, dy_lp, premasked=False):
-        xn, weff, qkv, o, wp_c, mask, B, L, pa, sa, pp, sp, prm, lse = saved
-        wqkv, bqkv, wl, bl, wp, bp = prm
+        s = saved
+        xn, prm = s.xn, s.prm
+        wqkv, _, _, _, wp, _ = prm
         M, D = xn.shape
         H, hd = self.H, D // self.H
-        dym = K.dropout(dy_lp, pp, sp) if (pp > 0 and not premasked) else dy_lp
-        do = lin_bwd_x(dym, wp_c, M, D, D, xn.dtype, site=wp)
-        dwp, dbp = self.proj_grads(dym, o, prm)
-        dqkv = K.mhla_attn_bwd(qkv, do, B, L, H, hd, self.W, mask, pa, sa, o=o if lse is not None else None, lse=lse)
-        dxn = lin_bwd_x(dqkv, weff, M, 3 * D, D, xn.dtype, site=wqkv)
+        dym = K.dropout(dy_lp, s.p_proj, s.seed_proj) if (s.p_proj > 0 and not premasked) else dy_lp
+        do = lin_bwd_x(dym, s.wp_c, M, D, D, xn.dtype, site=wp)
+        dwp, dbp = self.proj_grads(dym, s.o, prm)
+        dqkv = K.mhla_attn_bwd(s.qkv, do, s.B, s.L, H, hd, self.W, s.mask, s.p_attn, s.seed_attn,
+                               o=s.o if s.lse is not None else None, lse=s.lse)
+        dxn = lin_bwd_x(dqkv, s.weff, M, 3 * D, D, xn.dtype, site=wqkv)
         return dxn, self.qkv_grads(dqkv, xn, prm) + [dwp, dbp]
 
     @staticmethod
@@ -806,16 +812,19 @@ class MHLAChain:
         # (dW2, dW1, dWproj, dWeff join the grouped weight-gradient launch, which may wait for further blocks; the
         # batched fold below consumes dWeff only after that launch -- EncoderOp.bwd flushes in that order)
         tg = [_gt(p) for p in (wqkv, bqkv, wl, bl)]
-        if all(t is not None for t in tg) and _DEFER["on"]:
-            _DEFER["fold"].append((dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), tg, H, (wqkv, bqkv, wl, bl)))
+        q = _QUEUE
+        defer = q is not None and q.defer
+        if all(t is not None for t in tg) and defer:
+            q.folds.append(_Fold(dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), tg, H, (wqkv, bqkv, wl, bl)))
             return [None, None, None, None]
-        if (_DEFER["on"] and not wqkv.requires_grad and not bqkv.requires_grad and tg[2] is not None and tg[3] is not None):
+        if (defer and not wqkv.requires_grad and not bqkv.requires_grad and tg[2] is not None and tg[3] is not None):
             # frozen qkv projection, trainable latent_proj (experiments/sppp_mhla_pretrained.py:236-247): the batched
             # launch with its qkv half switched off, straight into the latent_proj gradient buffers
-            _DEFER["fold"].append((dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), [None, None, tg[2], tg[3]], H,
-                                   (wl, bl)))
+            q.folds.append(_Fold(dweff, dbeff, wqkv.detach(), bqkv.detach(), wl.detach(), [None, None, tg[2], tg[3]], H,
+                                 (wl, bl)))
             return [None, None, None, None]
-        flush_wgrads()                      # the fold runs now: dWeff must have been launched
+        if q is not None:
+            q.flush_wgrads()                # the fold runs now: dWeff must have been launched
         if all(t is not None for t in tg):
             with _side_stream(dweff, dbeff):
                 K.mhla_fold_bwd(dweff, dbeff, wqkv, bqkv, wl, H, out=tg)
@@ -840,46 +849,44 @@ class DenseChain:
         ld = 3 * D
         return (_View(t, 0, ld, L * ld, hd), _View(t, D, ld, L * ld, hd), _View(t, 2 * D, ld, L * ld, hd))
 
-    def fwd(self, xn, prm, B, L, residual, mask, training, ln=None):
+    def fwd(self, xn, prm, B, L, residual, mask, training):
         _check_mask_shape("DenseChain", mask, "key-keep [B, L]", (B, L))
         wqkv, bqkv, wp, bp = prm
-        M, D = xn.shape if ln is None else ln[0].shape
+        M, D = xn.shape
         H, hd = self.H, D // self.H
         pa = self.p_attn if training else 0.0
         pp = self.p_proj if (training and not self.torch_mha) else 0.0   # nn.MultiheadAttention has no proj dropout
         sa = _seed() if pa > 0 else 0
         sp = _seed() if pp > 0 else 0
         wqkv_c, wp_c = wcast(wqkv), wcast(wp)
-        if ln is not None:                       # LayerNorm fused into the qkv projection (see MHLAChain.fwd)
-            qkv, _, xn, mu, rs = lin_fwd_ln(ln[:3], wqkv_c, bqkv.detach(), M, 3 * D, D, get_compute_dtype())
-            ln[3][:] = [xn, mu, rs]
-        else:
-            qkv = lin_fwd(xn, wqkv_c, bqkv.detach(), M, 3 * D, D, xn.dtype, site=wqkv)
+        qkv = lin_fwd(xn, wqkv_c, bqkv.detach(), M, 3 * D, D, xn.dtype, site=wqkv)
         o = torch.empty((M, D), dtype=xn.dtype, device=xn.device)
         q, k, v = self._views(qkv, B, L, D, hd)
         ov = _View(o, 0, D, L * D, hd)
         att = sdpa_fwd(q, k, v, ov, B, H, L, L, hd, hd ** -0.5, mask, L if mask is not None else 0, 0, pa, sa)
         y = lin_fwd(o, wp_c, bp.detach(), M, D, D, torch.float32, residual=residual, drop=(pp, sp), site=wp)
-        return y, (xn, wqkv_c, qkv, o, wp_c, att, mask, B, L, pa, sa, pp, sp, prm)
+        return y, DenseSaved(xn=xn, wqkv_c=wqkv_c, qkv=qkv, o=o, wp_c=wp_c, att=att, mask=mask, B=B, L=L, p_attn=pa,
+                             seed_attn=sa, p_proj=pp, seed_proj=sp, prm=prm)
 
     @staticmethod
     def out_dropout(saved):
-        return saved[11], saved[12]
+        return saved.p_proj, saved.seed_proj
 
     def bwd(self, saved, dy_lp, premasked=False):
-        xn, wqkv_c, qkv, o, wp_c, att, mask, B, L, pa, sa, pp, sp, prm = saved
-        wqkv, bqkv, wp, bp = prm
+        s = saved
+        xn, qkv, o, mask, B, L = s.xn, s.qkv, s.o, s.mask, s.B, s.L
+        wqkv, bqkv, wp, bp = s.prm
         M, D = xn.shape
         H, hd = self.H, D // self.H
-        dym = K.dropout(dy_lp, pp, sp) if (pp > 0 and not premasked) else dy_lp
-        do = lin_bwd_x(dym, wp_c, M, D, D, xn.dtype, site=wp)
+        dym = K.dropout(dy_lp, s.p_proj, s.seed_proj) if (s.p_proj > 0 and not premasked) else dy_lp
+        do = lin_bwd_x(dym, s.wp_c, M, D, D, xn.dtype, site=wp)
         dwp, dbp = lin_bwd_w(dym, o, M, D, D, wp=wp, bp=bp)
         dqkv = torch.empty_like(qkv)
         q, k, v = self._views(qkv, B, L, D, hd)
         dq, dk, dv = self._views(dqkv, B, L, D, hd)
-        sdpa_bwd(q, k, v, _View(o, 0, D, L * D, hd), _View(do, 0, D, L * D, hd), dq, dk, dv, att, B, H, L, L, hd,
-                 hd ** -0.5, mask, L if mask is not None else 0, 0, pa, sa)
-        dxn = lin_bwd_x(dqkv, wqkv_c, M, 3 * D, D, xn.dtype, site=wqkv)
+        sdpa_bwd(q, k, v, _View(o, 0, D, L * D, hd), _View(do, 0, D, L * D, hd), dq, dk, dv, s.att, B, H, L, L, hd,
+                 hd ** -0.5, mask, L if mask is not None else 0, 0, s.p_attn, s.seed_attn)
+        dxn = lin_bwd_x(dqkv, s.wqkv_c, M, 3 * D, D, xn.dtype, site=wqkv)
         dwqkv, dbqkv = lin_bwd_w(dqkv, xn, M, 3 * D, D, wp=wqkv, bp=bqkv)
         return dxn, [dwqkv, dbqkv, dwp, dbp]
 
@@ -911,11 +918,14 @@ class CrossChain:
                        _View(o, 0, D, Lq * D, hd), B, H, Lq, Lk, hd, scale, mask,
                        Lq * Lk if mask is not None else 0, Lk if mask is not None else 0, pa, sa)
         y = lin_fwd(o, wo_c, bo.detach(), B * Lq, D, D, torch.float32, residual=residual)
-        return y, (qn, kn, q, k, v, o, (wq_c, wk_c, wv_c, wo_c), att, mask, B, Lq, Lk, pa, sa, scale, prm)
+        return y, CrossSaved(qn=qn, kn=kn, q=q, k=k, v=v, o=o, w_c=(wq_c, wk_c, wv_c, wo_c), att=att, mask=mask, B=B,
+                             Lq=Lq, Lk=Lk, p_attn=pa, seed_attn=sa, scale=scale, prm=prm)
 
     def bwd(self, saved, dy_lp):
-        qn, kn, q, k, v, o, (wq_c, wk_c, wv_c, wo_c), att, mask, B, Lq, Lk, pa, sa, scale, prm = saved
-        wq, bq, wk, bk, wv, bv, wo, bo = prm
+        s = saved
+        qn, kn, q, k, v, o, att, mask, B, Lq, Lk = s.qn, s.kn, s.q, s.k, s.v, s.o, s.att, s.mask, s.B, s.Lq, s.Lk
+        (wq_c, wk_c, wv_c, wo_c), pa, sa, scale = s.w_c, s.p_attn, s.seed_attn, s.scale
+        wq, bq, wk, bk, wv, bv, wo, bo = s.prm
         D = qn.shape[1]
         H, hd = self.H, D // self.H
         cdt = qn.dtype
@@ -954,9 +964,9 @@ class MLPChain:
         self.p = p
         self.names = (f"{fc1}.weight", f"{fc1}.bias", f"{fc2}.weight", f"{fc2}.bias")
 
-    def fwd(self, xn, prm, residual, training, ln=None):
+    def fwd(self, xn, prm, residual, training):
         w1, b1, w2, b2 = prm
-        M, D = xn.shape if ln is None else ln[0].shape
+        M, D = xn.shape
         Hd = w1.shape[0]
         Do = w2.shape[0]
         p = self.p if training else 0.0
@@ -966,17 +976,11 @@ class MLPChain:
         # Low-precision path: the fc1 epilogue saves GELU'(u) (Phi and phi share one exponential) instead of u, so the
         # backward epilogue is a multiply: the GELU arithmetic (~20 VALU slots per element) runs once instead of twice
         # (measured: -0.09 ms per cfg2 step; both epilogues stay bound by their 310 MB of HBM traffic).  The fp32 parity mode keeps the pre-activation and the exact erf.
-        if ln is not None:                       # LayerNorm fused into fc1 (bf16 mode only: see EncoderOp.fwd)
-            sg = True
-            h, pre, xn, mu, rs = lin_fwd_ln(ln[:3], w1_c, b1.detach(), M, Hd, D, get_compute_dtype(), act=ACT_GELU_SAVEGRAD,
-                                            want_pre=True, drop=(p, s1))
-            ln[3][:] = [xn, mu, rs]
-        else:
-            sg = self.saves_gelu_grad(xn.dtype)
-            h, pre = lin_fwd(xn, w1_c, b1.detach(), M, Hd, D, xn.dtype, act=ACT_GELU_SAVEGRAD if sg else ACT_GELU,
-                             want_pre=True, drop=(p, s1), site=w1)
+        sg = self.saves_gelu_grad(xn.dtype)
+        h, pre = lin_fwd(xn, w1_c, b1.detach(), M, Hd, D, xn.dtype, act=ACT_GELU_SAVEGRAD if sg else ACT_GELU,
+                         want_pre=True, drop=(p, s1), site=w1)
         y = lin_fwd(h, w2_c, b2.detach(), M, Do, Hd, torch.float32, residual=residual, drop=(p, s2), site=w2)
-        return y, (xn, (pre, sg), h, w1_c, w2_c, p, s1, s2, prm)
+        return y, MLPSaved(xn=xn, pre=pre, pre_is_grad=sg, h=h, w1_c=w1_c, w2_c=w2_c, p=p, seed_fc1=s1, seed_fc2=s2, prm=prm)
 
     @staticmethod
     def saves_gelu_grad(cdt) -> bool:
@@ -986,17 +990,19 @@ class MLPChain:
 
     @staticmethod
     def out_dropout(saved):
-        return saved[5], saved[7]
+        return saved.p, saved.seed_fc2
 
     def bwd(self, saved, dy_lp, premasked=False):
-        xn, (pre, sg), h, w1_c, w2_c, p, s1, s2, prm = saved
-        w1, b1, w2, b2 = prm
+        s = saved
+        xn, prm, p = s.xn, s.prm, s.p
+        w1, _, w2, _ = prm
         M, D = xn.shape
-        Hd, Do = w1_c.shape[0], w2_c.shape[0]
-        dym = K.dropout(dy_lp, p, s2) if (p > 0 and not premasked) else dy_lp
-        dpre = lin_bwd_x(dym, w2_c, M, Do, Hd, xn.dtype, dgelu_pre=pre, pre_is_grad=sg, drop=(p, s1), site=w2)
-        dw2, db2 = self.fc2_grads(dym, h, prm)
-        dxn = lin_bwd_x(dpre, w1_c, M, Hd, D, xn.dtype, site=w1)
+        Hd, Do = s.w1_c.shape[0], s.w2_c.shape[0]
+        dym = K.dropout(dy_lp, p, s.seed_fc2) if (p > 0 and not premasked) else dy_lp
+        dpre = lin_bwd_x(dym, s.w2_c, M, Do, Hd, xn.dtype, dgelu_pre=s.pre, pre_is_grad=s.pre_is_grad, drop=(p, s.seed_fc1),
+                         site=w2)
+        dw2, db2 = self.fc2_grads(dym, s.h, prm)
+        dxn = lin_bwd_x(dpre, s.w1_c, M, Hd, D, xn.dtype, site=w1)
         dw1, db1 = self.fc1_grads(dpre, xn, prm)
         return dxn, [dw1, db1, dw2, db2]
 
@@ -1229,9 +1235,9 @@ def set_native_blocks(on: bool) -> None:
 
 
 def _native_blocks_on() -> bool:
-    """The conditions that do not depend on the block.  K.GEMM_TRACE has to see every GEMM; the side stream and the
-    fused LayerNorm are launch patterns of the Python chains only."""
-    return (_NATIVE["on"] and K.GEMM_TRACE is None and not _SIDE["enabled"] and not _LN_FUSE
+    """The conditions that do not depend on the block.  K.GEMM_TRACE has to see every GEMM; the side stream is a
+    launch pattern of the Python chains only."""
+    return (_NATIVE["on"] and K.GEMM_TRACE is None and not _SIDE["enabled"]
             and get_compute_mode() == "bf16" and not os.environ.get("FAVIT_NO_NATIVE_BLOCKS"))
 
 
@@ -1298,14 +1304,16 @@ class _NativeTape:
             pl = self.plan
             M, D = pl.M, pl.D
             lse = self.f32("lse", pl.B, pl.H, pl.n) if pl.off["lse"][1] else None
-            self.sa = (self.bf("xn1", M, D), self.weff, self.bf("qkv", M, 3 * D), self.bf("o", M, D), self.wc[0], None,
-                       pl.B, pl.n, 0.0, 0, 0.0, 0, self.pa, lse)
+            self.sa = MHLASaved(xn=self.bf("xn1", M, D), weff=self.weff, qkv=self.bf("qkv", M, 3 * D), o=self.bf("o", M, D),
+                                wp_c=self.wc[0], mask=None, B=pl.B, L=pl.n, p_attn=0.0, seed_attn=0, p_proj=0.0,
+                                seed_proj=0, prm=self.pa, lse=lse)
             self.mu1, self.rs1 = self.f32("mu1", M), self.f32("rs1", M)
         elif name in ("x1", "mu2", "rs2", "sm"):
             pl = self.plan
             Mm, D, Hd = pl.Mm, pl.D, pl.hidden
-            self.sm = (self.bf("xn2", Mm, D), (self.bf("pre", Mm, Hd), MLPChain.saves_gelu_grad(torch.bfloat16)),
-                       self.bf("h", Mm, Hd), self.wc[1], self.wc[2], 0.0, 0, 0, self.pm)
+            self.sm = MLPSaved(xn=self.bf("xn2", Mm, D), pre=self.bf("pre", Mm, Hd),
+                               pre_is_grad=MLPChain.saves_gelu_grad(torch.bfloat16), h=self.bf("h", Mm, Hd),
+                               w1_c=self.wc[1], w2_c=self.wc[2], p=0.0, seed_fc1=0, seed_fc2=0, prm=self.pm)
             self.mu2, self.rs2 = self.f32("mu2", Mm), self.f32("rs2", Mm)
             if self.mcut is None:
                 self.x1 = self.f32("x1", pl.M, D)
@@ -1355,11 +1363,6 @@ class EncoderOp:
         cdt = get_compute_dtype()
         x = _as_f32(x).reshape(M, D)
         tapes = []
-        # short token counts, bf16: the two LayerNorms of a block ride in the A-operand staging of the qkv / fc1
-        # projections (favit_ln_gemm; the library declines shapes beyond the 64-row kernel's regime, and
-        # lin_fwd_ln then issues the two launches)
-        # (evaluated per block: a CLS-only encoder's blocks run on different row counts; the switch is off by default)
-        fuse_ok = _LN_FUSE and cdt == torch.bfloat16 and get_compute_mode() == "bf16" and D % 64 == 0 and D <= 512
         # the latent_proj folds only depend on parameters: all MHLA blocks of equal geometry in ONE launch
         pre = [None] * len(self.blocks)
         idx, fp, off = [], [], 0
@@ -1395,7 +1398,7 @@ class EncoderOp:
             nt = self._fwd_native(bs, p, x, B, L, D, pre[bi], cut, mc) if native and pre[bi] is not None else None
             dpa = dpm = None
             if nt is None:
-                x1, mu1, rs1, sa = self._attn_half_fwd(bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre[bi], branch=dp > 0)
+                x1, mu1, rs1, sa = self._attn_half_fwd(bs, pa, x, g1, b1, B, L, D, cdt, pre[bi], branch=dp > 0)
                 if dp > 0:                    # x1 holds the branch: the sum goes back into it
                     dpa = (dp, _seed())
                     x1 = K.drop_path_add(x, x1, B, L, D, dp, dpa[1], out=x1)
@@ -1410,7 +1413,7 @@ class EncoderOp:
                 M = B * L
             # 4. the MLP half, x2 = x1 + mlp(LN2(x1)), and the block's tape
             if nt is None:
-                xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok, branch=dp > 0)
+                xn2, mu2, rs2, sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, branch=dp > 0)
                 if dp > 0:                    # (L: the rows of this half, behind mcut)
                     dpm = (dp, _seed())
                     x2 = K.drop_path_add(x1, x2, B, L, D, dp, dpm[1], out=x2)
@@ -1424,7 +1427,7 @@ class EncoderOp:
                 nt.mcut, nt.x1 = mcut, x1
                 if K.mhla_block_mlp_fwd(nt.plan, x1) != 0:
                     nt.mlp_in_tape = False
-                    _, nt.mu2, nt.rs2, nt.sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt, fuse_ok)
+                    _, nt.mu2, nt.rs2, nt.sm, x2 = self._mlp_half_fwd(bs, pm, x1, g2, b2, M, D, cdt)
             tapes.append(nt)
             x = nt.f32("x2", M, D) if nt.mlp_in_tape else x2
         return x.reshape(B, L, D), (tapes, B, L_in, D)
@@ -1433,31 +1436,19 @@ class EncoderOp:
         """The stochastic depth rate in force for both halves of block bs: its rate in training mode, else 0."""
         return bs.drop_path if self.training else 0.0
 
-    def _attn_half_fwd(self, bs, pa, x, g1, b1, B, L, D, cdt, fuse_ok, pre, branch=False):
+    def _attn_half_fwd(self, bs, pa, x, g1, b1, B, L, D, cdt, pre, branch=False):
         """LayerNorm 1 and the attention chain on the B * L rows of x (the Python chains).  branch: the chain runs
         without its residual and the first result is attn(LN1(x)) alone (a dropped half)."""
         M = B * L
         kw = {"pre": pre} if pre is not None else {}
-        res = None if branch else x
-        if fuse_ok and M <= 16384 and isinstance(bs.attn, (MHLAChain, DenseChain)):
-            o1 = [None, None, None]
-            x1, sa = bs.attn.fwd(None, pa, B, L, res, self.mask, self.training, ln=(x, g1.detach(), b1.detach(), o1), **kw)
-            xn1, mu1, rs1 = o1
-        else:
-            xn1, mu1, rs1 = K.layernorm_fwd(x, D, g1, b1, M, D, cdt, q8=_q8_request(bs.attn, pa, "fwd", D))
-            x1, sa = bs.attn.fwd(xn1, pa, B, L, res, self.mask, self.training, **kw)
+        xn1, mu1, rs1 = K.layernorm_fwd(x, D, g1, b1, M, D, cdt, q8=_q8_request(bs.attn, pa, "fwd", D))
+        x1, sa = bs.attn.fwd(xn1, pa, B, L, None if branch else x, self.mask, self.training, **kw)
         return x1, mu1, rs1, sa
 
-    def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, fuse_ok, branch=False):
+    def _mlp_half_fwd(self, bs, pm, x1, g2, b2, M, D, cdt, branch=False):
         """LayerNorm 2 and the MLP chain on the M rows of x1 (the Python chains).  branch: as in _attn_half_fwd."""
-        res = None if branch else x1
-        if fuse_ok and M <= 16384 and isinstance(bs.mlp, MLPChain):
-            o2 = [None, None, None]
-            x2, sm = bs.mlp.fwd(None, pm, res, self.training, ln=(x1, g2.detach(), b2.detach(), o2))
-            xn2, mu2, rs2 = o2
-        else:
-            xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
-            x2, sm = bs.mlp.fwd(xn2, pm, res, self.training)
+        xn2, mu2, rs2 = K.layernorm_fwd(x1, D, g2, b2, M, D, cdt, q8=_q8_request(bs.mlp, pm, "fwd", D))
+        x2, sm = bs.mlp.fwd(xn2, pm, None if branch else x1, self.training)
         return xn2, mu2, rs2, sm, x2
 
     def _fwd_native(self, bs, p, x, B, L, D, pre, cut, mc):
@@ -1513,7 +1504,7 @@ class EncoderOp:
         the stream (ptrs_set), LayerNorm 2 has its gradient buffers, and g / g_lp come from the row cut.  Plans are
         shared by every tape of one shape: in any other case the pointers have to be written again.
         Lifetime: every buffer the queued launches read or write is a VIEW of the arena or of the tape, held by
-        _WG["list"] / _DEFER until those launches have been issued; nothing is freed or reused before."""
+        the backward queue (_QUEUE) until those launches have been issued; nothing is freed or reused before."""
         plan = tp.plan
         g1, g2 = tp.ln1[0], tp.ln2[0]
         tg = [_gt(q) for q in (tp.ln1 if handed is not None else tp.ln1 + tp.ln2)]
@@ -1536,13 +1527,13 @@ class EncoderOp:
         if tp.mcut is None:                   # the whole block: its MLP half's problems and fold come first
             dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", M, Hd), tp.pm)
             dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (M, Hd)), tp.bf("xn2", M, D), tp.pm)
-            _DEFER["ln"].append((part("part2"), tg[2], tg[3], tp.ln2))
+            _QUEUE.ln_folds.append(_LNFold(part("part2"), tg[2], tg[3], tp.ln2))
             gm = [dw1, db1, dw2, db2]
             g_lp = _carve(abf, bo["g1_lp"][0] // 2, (M, D))         # the gradient of x1 the call left
         dqkv = _carve(abf, bo["dqkv"][0] // 2, (M, 3 * D))
         dwp, dbp = bs.attn.proj_grads(g_lp, tp.bf("o", M, D), tp.pa)
         ga = bs.attn.qkv_grads(dqkv, tp.bf("xn1", M, D), tp.pa) + [dwp, dbp]
-        _DEFER["ln"].append((part("part1"), tg[0], tg[1], tp.ln1))
+        _QUEUE.ln_folds.append(_LNFold(part("part1"), tg[0], tg[1], tp.ln1))
         g_out = _carve(af, bo["g_out_f32"][0] // 4, (M, D))
         return g_out, (_carve(abf, bo["g_out_lp"][0] // 2, (M, D)) if want_lp else None), ga, gm
 
@@ -1568,7 +1559,7 @@ class EncoderOp:
         abf, af = arena.view(torch.bfloat16), arena.view(torch.float32)
         dw2, db2 = bs.mlp.fc2_grads(g_lp, tp.bf("h", Mm, Hd), tp.pm)
         dw1, db1 = bs.mlp.fc1_grads(_carve(abf, bo["dpre"][0] // 2, (Mm, Hd)), tp.bf("xn2", Mm, D), tp.pm)
-        _DEFER["ln"].append((_carve(af, bo["part2"][0] // 4, (2, plan.nparts2, D)), tg2, tb2, tp.ln2))
+        _QUEUE.ln_folds.append(_LNFold(_carve(af, bo["part2"][0] // 4, (2, plan.nparts2, D)), tg2, tb2, tp.ln2))
         g1_f32 = _carve(af, bo["g1_f32"][0] // 4, (Mm, D))
         return g1_f32, None, [None, None], [dw1, db1, dw2, db2], torch.bfloat16, (arena, abf, af)
 
@@ -1582,12 +1573,12 @@ class EncoderOp:
         if not gam.requires_grad and not bet.requires_grad:      # frozen layer: no dgamma / dbeta fold at all
             return K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, lp_drop=pd, frozen=True, q8=q8)
         tg_, tb_ = _gt(gam), _gt(bet)
-        lst = _DEFER["ln"] if (_DEFER["on"] and tg_ is not None and tb_ is not None) else None
-        n0 = len(lst) if lst is not None else 0
+        q = _QUEUE
+        lst = [] if (q is not None and q.defer and tg_ is not None and tb_ is not None) else None
         out = K.layernorm_bwd(dxn, xin, D, gam, mu, rs, M, D, dres=dres, want_lp=want_lp, dg_out=tg_, db_out=tb_,
                               lp_drop=pd, defer=lst, q8=q8)
         if lst is not None:
-            lst[n0] = lst[n0] + ((gam, bet),)
+            q.ln_folds.extend(_LNFold(*e, ready=(gam, bet)) for e in lst)
         elif out[2] is None:
             _ready(gam, bet)
         return out
@@ -1631,9 +1622,6 @@ class EncoderOp:
         cdt = get_compute_dtype()
         g_lp = g if tapes and tapes[-1].dpm is not None else _as_cdt(g)      # (a dropped half makes its own copy)
         grads = []
-        begin_wgrads(per_block=any(tp.cut is not None or tp.mcut is not None for tp in tapes))
-        begin_deferred()
-        begin_zero_pool(sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)), dy.device)
 
         def expand(g, cut, lp_dtype):
             # back over a row cut: zeros in the rows it dropped, and the compute-dtype copy the next backward GEMMs read
@@ -1642,7 +1630,9 @@ class EncoderOp:
             g, g_lp = K.rows_cut_bwd(g, B, n_in, ca, cb, D, lp_dtype=lp_dtype)
             g = g.reshape(B * n_in, D)
             return g, (g_lp.reshape(B * n_in, D) if g_lp is not None else g)
-        try:
+        with _BackwardQueue(per_block=any(tp.cut is not None or tp.mcut is not None for tp in tapes),
+                            zero_floats=sum(3 * D + 4 for bs in self.blocks if isinstance(bs.attn, MHLAChain)),
+                            device=dy.device) as queue:
             # The low-precision copy of the stream gradient only feeds the next branch's backward GEMMs; when that
             # branch's output was dropped in forward, the LayerNorm backward that produces the copy applies the mask
             # (no separate masking pass: 24 launches of 28 us per cfg2 step at dropout 0.1).
@@ -1658,7 +1648,7 @@ class EncoderOp:
                     q8n = _q8_request(nbs.mlp, ntp.pm, "bwd", D)       # the next block's fc2 input-gradient GEMM
                 # the block below starts with a dropped half: it makes its copy itself, none is written for it
                 lp_below = ntp is not None and ntp.dpm is None
-                nat_ok = (tp.native and not premasked and pd_n[0] == 0 and q8n is None and _DEFER["on"]
+                nat_ok = (tp.native and not premasked and pd_n[0] == 0 and q8n is None and queue.defer
                           and _native_blocks_on())
                 whole = self._bwd_native(bs, tp, g, g_lp) if nat_ok and tp.mcut is None else None
                 if whole is not None:         # the block without an inner cut: ONE library call
@@ -1681,22 +1671,11 @@ class EncoderOp:
                 if tp.cut is not None:
                     # this block ran on its (head, tail) rows: back to the rows of the block below
                     g, g_lp = expand(g, tp.cut, lp_dt if lp_below and g.dtype != lp_dt else None)
-                if flush_wgrads(force=False, next_rows=(tp.rows, ntp.rows) if ntp is not None else None) \
-                        and _STATE["grad_ready"] is not None:
-                    flush_deferred()
+                if queue.end_block((tp.rows, ntp.rows) if ntp is not None else None) and _STATE["grad_ready"] is not None:
+                    queue.flush_deferred()
                 if not _SIDE["enabled"]:
                     join_side_stream()
                 grads = ln1_g + ga + ln2_g + gm + grads
-        except BaseException:
-            _WG["list"] = None                # drop the half-collected weight gradients of the failed backward
-            _SIDE["pending"].clear()
-            _DEFER.update(on=False, fold=[], ln=[])
-            end_zero_pool()
-            raise
-        end_wgrads()
-        end_deferred()
-        end_zero_pool()
-        join_side_stream()
         return [g.reshape(B, L, D)], grads
 
 

@@ -189,6 +189,49 @@ def test_symbols_and_abi_version(favit):
     assert lib.favit_abi_version() == 8
 
 
+@pytest.mark.parametrize("training", [False, True])
+def test_native_tape_builds_the_chains_records(favit, training):
+    """What the Python backward reads from a native tape are the chains' own records, every tensor field a view of its
+    plan.off slot, every dropout field zero (a block with an active dropout never runs the native chain)."""
+    import torch
+    F = favit.functional
+    B, n, D, H, W, hidden = 3, 17, 128, 2, 7, 512
+    plan = favit.kernels.mhla_block_plan(B, n, D, H, W, hidden, training)
+    buf = torch.zeros(plan.tape_bytes, dtype=torch.uint8)
+    pa, pm, weff, wc = [object()] * 6, [object()] * 4, object(), (object(), object(), object())
+    tp = F._NativeTape(plan, buf, None, (None, None), (None, None), pa, pm, weff, wc, None)
+    M, f32, bf16 = B * n, torch.float32, torch.bfloat16
+
+    def check(t, slot, shape, dtype):
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous(), slot
+        assert t.data_ptr() - buf.data_ptr() == plan.off[slot][0], slot
+        assert t.numel() * t.element_size() <= plan.off[slot][1], slot
+    sa, sm = tp.sa, tp.sm
+    assert type(sa) is F.MHLASaved and type(sm) is F.MLPSaved
+    check(sa.xn, "xn1", (M, D), bf16)
+    check(sa.qkv, "qkv", (M, 3 * D), bf16)
+    check(sa.o, "o", (M, D), bf16)
+    check(tp.mu1, "mu1", (M,), f32)
+    check(tp.rs1, "rs1", (M,), f32)
+    if training:
+        check(sa.lse, "lse", (B, H, n), f32)
+    else:
+        assert sa.lse is None
+    assert sa.weff is weff and sa.wp_c is wc[0] and sa.prm is pa and sa.mask is None and (sa.B, sa.L) == (B, n)
+    assert (sa.p_attn, sa.seed_attn, sa.p_proj, sa.seed_proj) == (0.0, 0, 0.0, 0)
+    assert F.MHLAChain.out_dropout(sa) == (0.0, 0)
+    check(sm.xn, "xn2", (M, D), bf16)
+    check(sm.pre, "pre", (M, hidden), bf16)
+    check(sm.h, "h", (M, hidden), bf16)
+    check(tp.mu2, "mu2", (M,), f32)
+    check(tp.rs2, "rs2", (M,), f32)
+    check(tp.x1, "x1", (M, D), f32)
+    assert sm.pre_is_grad is True and sm.w1_c is wc[1] and sm.w2_c is wc[2] and sm.prm is pm
+    assert (sm.p, sm.seed_fc1, sm.seed_fc2) == (0.0, 0, 0)
+    assert F.MLPChain.out_dropout(sm) == (0.0, 0)
+    assert tp.sa is sa and tp.sm is sm, "made once"
+
+
 def test_switches(favit, monkeypatch):
     F = favit.functional
     favit.set_compute_dtype("bf16")
