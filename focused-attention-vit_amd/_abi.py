@@ -122,6 +122,8 @@ POOL = {k[len("FAVIT_POOL_"):].lower(): v for k, v in CONSTS.items() if k.starts
 # the slot NAMES of the two block layouts, in the order of their offsets (these replace the two counts of the header)
 BLOCK_TAPE_SLOTS = _slot_names("FAVIT_TAPE_", CONSTS["FAVIT_BLOCK_TAPE_SLOTS"])
 BLOCK_BWD_SLOTS = _slot_names("FAVIT_BWD_", CONSTS["FAVIT_BLOCK_BWD_SLOTS"])
+# the slots of favit_eval_metrics' state; the last one, hits, is EVAL_MAX_TOPK words long
+EVAL_SLOTS = _slot_names("FAVIT_EVAL_SLOT_", CONSTS["FAVIT_EVAL_STATE_WORDS"] - CONSTS["FAVIT_EVAL_MAX_TOPK"] + 1)
 
 _lib = None
 

@@ -1217,6 +1217,57 @@ def cross_entropy(logits, labels, grad_scale=None, label_smoothing=0.0, mix_lam=
     return loss_rows, dlog
 
 
+EVAL_MAX_TOPK = _abi.EVAL_MAX_TOPK
+EVAL_STATE_WORDS = _abi.EVAL_STATE_WORDS
+EVAL_SLOTS = {name: i for i, name in enumerate(_abi.EVAL_SLOTS)}      # loss_sum, batch_mean_sum, rows, ..., hits
+
+
+def check_topk(topk):
+    """The k values of eval_metrics as a tuple: at most EVAL_MAX_TOPK integers, each >= 1 (checked without a GPU)."""
+    ks = tuple(topk)
+    if len(ks) > EVAL_MAX_TOPK:
+        raise ValueError(f"eval_metrics: at most {EVAL_MAX_TOPK} top-k values per launch, got {len(ks)}")
+    for k in ks:
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"eval_metrics: every k must be an integer >= 1, got {k!r}")
+    return tuple(min(k, 2 ** 31 - 1) for k in ks)
+
+
+def eval_metrics(logits, labels, state, loss_rows, pred_rows, rank_rows, topk=(1,), class_total=None,
+                 class_correct=None, confusion=None):
+    """favit_eval_metrics: two launches, no sync.  logits fp32 [B, C] (rows may be strided, columns not), labels
+    int64 [B].  Written: loss_rows fp32, pred_rows / rank_rows int32, [>= B] each (row b: the cross-entropy, the argmax
+    with the lowest index on ties, the label's place in a stable descending sort; a label outside [0, C) is ignored: NaN,
+    -1, -1).  ADDED to: state, int64 [EVAL_STATE_WORDS] (EVAL_SLOTS names the words; loss_sum and batch_mean_sum hold
+    doubles: read them through state.view(torch.float64)), and the optional int64 class_total [C], class_correct [C],
+    confusion [C, C] (row = label, column = prediction).  The caller zeroes what is added to."""
+    ks = check_topk(topk)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype != torch.float32 \
+            or (logits.shape[1] > 1 and logits.stride(1) != 1) or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1]):
+        raise TypeError("eval_metrics: logits must be an fp32 [B, C] tensor with contiguous rows")
+    B, Cn = logits.shape
+    if Cn < 1:
+        raise ValueError("eval_metrics: no classes")
+    require_gpu(logits, labels, state, loss_rows, pred_rows, rank_rows, class_total, class_correct, confusion)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise TypeError("eval_metrics: labels must be a contiguous int64 [B] tensor")
+    if state.dtype != torch.int64 or state.numel() != EVAL_STATE_WORDS or not state.is_contiguous():
+        raise TypeError(f"eval_metrics: state must be {EVAL_STATE_WORDS} contiguous int64")
+    for name, t, dt in (("loss_rows", loss_rows, torch.float32), ("pred_rows", pred_rows, torch.int32),
+                        ("rank_rows", rank_rows, torch.int32)):
+        if t.dtype != dt or t.dim() != 1 or t.numel() < B or not t.is_contiguous():
+            raise TypeError(f"eval_metrics: {name} must be a contiguous {dt} vector of at least {B} elements")
+    for name, t, n in (("class_total", class_total, Cn), ("class_correct", class_correct, Cn),
+                       ("confusion", confusion, Cn * Cn)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous()):
+            raise TypeError(f"eval_metrics: {name} must be {n} contiguous int64")
+    ld = logits.stride(0) if B > 1 else Cn
+    k4 = ks + (0,) * (EVAL_MAX_TOPK - len(ks))
+    _abi.check(_abi.lib().favit_eval_metrics(_p(logits), ld, _p(labels), _p(loss_rows), _p(pred_rows), _p(rank_rows),
+                                             _p(state), _p(class_total), _p(class_correct), _p(confusion), B, Cn,
+                                             len(ks), k4[0], k4[1], k4[2], k4[3], _st()), "favit_eval_metrics")
+
+
 GRAD_NORM_MAX_BUFS = _abi.GRAD_NORM_MAX_BUFS
 
 

@@ -818,6 +818,48 @@ int favit_cross_entropy_distill(const float* logits, const float* teacher, const
                                 int32_t B, int32_t C, float grad_scale, float label_smoothing,
                                 float alpha, float tau, int32_t hard, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Evaluation metrics (additive in ABI 8; csrc/eval.hip): loss, top-k hits, per-class counts
+ * and a confusion matrix of a batch of logits, ADDED to a device-resident state.  Nothing synchronises; a validation
+ * pass reads the state once at its end.  x = logits fp32 [B, C] with row stride ld >= C (elements), y = labels
+ * int64 [B].
+ * ---------------------------------------------------------------------------------- */
+#define FAVIT_EVAL_MAX_TOPK 4       /* k values per launch */
+#define FAVIT_EVAL_STATE_WORDS 10   /* 8-byte words of `state`: the slots below, HITS being FAVIT_EVAL_MAX_TOPK words */
+enum {   /* index of every slot in `state`; LOSS_SUM and BATCH_MEAN_SUM hold doubles, the others int64 */
+  FAVIT_EVAL_SLOT_LOSS_SUM = 0, FAVIT_EVAL_SLOT_BATCH_MEAN_SUM = 1, FAVIT_EVAL_SLOT_ROWS = 2,
+  FAVIT_EVAL_SLOT_BATCHES = 3, FAVIT_EVAL_SLOT_IGNORED = 4, FAVIT_EVAL_SLOT_NONFINITE = 5, FAVIT_EVAL_SLOT_HITS = 6
+};
+/* Per row b, written to the caller's loss_rows fp32 [B], pred_rows int32 [B], rank_rows int32 [B] (all three required:
+ * they are the hand-off between the two launches, and a per-sample result):
+ *   loss[b] = lse(x_b) - x_b[y_b]                       the row of favit_cross_entropy, by the same expressions
+ *   pred[b] = argmax_c x_b[c], the lowest index on ties
+ *   rank[b] = #{c : x_c > x_y} + #{c < y : x_c == x_y}  the label's place in a stable descending sort: top-k hits
+ *             iff rank < k, and rank == 0 iff pred == y
+ *   y_b outside [0, C): the row is IGNORED: loss = NaN, pred = rank = -1, only the `ignored` counter moves and the
+ *             logits of the row are not read (a batch padded with labels of -1 is evaluated this way)
+ *   y_b valid and loss[b] not finite (a NaN or +inf anywhere in the row, -inf at the label, an all -inf row; a -inf on
+ *             another class is legitimate and stays finite): pred = rank = -1; the row counts in rows, nonfinite and
+ *             class_total[y] and adds its loss to both sums (a NaN model shows a NaN loss), hits no k and enters
+ *             neither class_correct nor confusion.
+ * Added to state (FAVIT_EVAL_STATE_WORDS 8-byte words, 8-byte aligned, zeroed by the caller before the first launch):
+ *   LOSS_SUM (double) += the sum of the valid rows' losses;  BATCH_MEAN_SUM (double) += that sum / valid rows and
+ *   BATCHES += 1 -- a launch without a valid row adds nothing to either and is no batch;  ROWS += valid rows;
+ *   IGNORED, NONFINITE += those rows;  HITS + i += rows with rank < k_i, i < n_topk (k_i >= C always hits).
+ * Optional (NULL: skipped), int64, zeroed by the caller:  class_total [C] += valid rows per label;  class_correct [C]
+ *   += rows with pred == y per label;  confusion [C * C] += 1 at [y * C + pred].
+ * Two launches: one wave per row, four rows per 256-thread workgroup, any C >= 1; then ONE workgroup that adds the
+ * row records in a fixed order, the losses in double precision, looping when B exceeds its 256 threads.  No atomics on
+ * floats: the same inputs give the same bits of `state` in every run.  The per-class and confusion counts are integer
+ * atomics (integer adds commute, so they are reproducible as well).
+ * Refused with FAVIT_ERR_INVALID before any launch, the state untouched: NULL logits, labels, state, loss_rows,
+ * pred_rows or rank_rows; C < 1; B < 0; ld < C; n_topk outside 0..FAVIT_EVAL_MAX_TOPK; a k_i < 1 with i < n_topk
+ * (the k beyond n_topk are not read).  B == 0 is FAVIT_OK and changes nothing.  The health word is not touched. */
+int favit_eval_metrics(const float* logits, int64_t ld, const int64_t* labels, float* loss_rows, int32_t* pred_rows,
+                       int32_t* rank_rows, int64_t* state, int64_t* class_total /* [C] or NULL */,
+                       int64_t* class_correct /* [C] or NULL */, int64_t* confusion /* [C * C] or NULL */, int32_t B,
+                       int32_t C, int32_t n_topk, int32_t k0, int32_t k1, int32_t k2, int32_t k3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,7 +236,22 @@ def parse_args(argv=None):
     ap.add_argument("--distill_tau", type=float, default=1.0, help="--distill_type soft: the temperature")
     ap.add_argument("--distill_type", default="soft", choices=["soft", "hard"],
                     help="soft: tau^2 * KL(teacher || student) at temperature tau; hard: cross-entropy against the teacher's argmax")
+    ap.add_argument("--eval_topk", type=int, nargs="+", default=None, metavar="K",
+                    help="validate and test through the device metrics (harness.EvalMetrics) and report top-K accuracy for "
+                         "up to 4 values, e.g. 1 5; 1 is always included; a K above the class count always hits; the CSV "
+                         "gains test_top{K} columns (default: the evaluation and the columns of before)")
+    ap.add_argument("--eval_per_class", action="store_true", help="print the per-class test accuracy (device metrics)")
+    ap.add_argument("--eval_confusion", default=None, metavar="PATH",
+                    help="write the test confusion matrix (row = label, column = prediction) as .npy (device metrics)")
+    ap.add_argument("--eval_graph", action="store_true",
+                    help="replay every evaluation batch as one HIP graph (harness.GraphedEval; device metrics)")
     a = ap.parse_args(argv)
+    if a.eval_topk is not None:
+        if any(k < 1 for k in a.eval_topk):
+            ap.error("--eval_topk: every K must be >= 1")
+        a.eval_topk = sorted(set(a.eval_topk) | {1})
+        if len(a.eval_topk) > 4:
+            ap.error("--eval_topk takes at most 4 values (1 included)")
     if not 0.0 <= a.distill_alpha <= 1.0:
         ap.error("--distill_alpha must be in [0, 1]")
     if a.distill_alpha > 0 and a.teacher_experiment is None:
@@ -338,15 +353,23 @@ def main(argv=None):
     if a.lr_schedule == "cosine":
         per_epoch = max(1, len(train_src))
         schedule = pkg.train.WarmupCosine(opt, int(round(a.warmup_epochs * per_epoch)), max(1, a.epochs * per_epoch))
+    metrics, fit_kw, eval_kw = None, {}, {}          # (none of the four flags: exactly the evaluation of before)
+    if a.eval_topk is not None or a.eval_per_class or a.eval_confusion is not None or a.eval_graph:
+        metrics = pkg.harness.EvalMetrics(classes, topk=a.eval_topk or (1,), per_class=a.eval_per_class,
+                                          confusion=a.eval_confusion is not None)
+        fit_kw = {"eval_metrics": metrics, "eval_graph": a.eval_graph}
+        eval_kw = {"metrics": metrics, "graph": a.eval_graph, "opt": opt}
     with torch.cuda.stream(work):
         res = pkg.harness.fit(run, train_loader, test_loader, opt, a.epochs, label_smoothing=a.label_smoothing,
                               schedule=schedule, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
-                              resume=a.resume, eval_ema=a.eval_ema, teacher=teacher, distill=distill)
+                              resume=a.resume, eval_ema=a.eval_ema, teacher=teacher, distill=distill, **fit_kw)
+        if metrics is not None:
+            metrics.reset()
         if a.eval_ema:
             with opt.ema_weights():
-                ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
+                ev = pkg.harness.evaluate(run, test_loader, a.batch_size, **eval_kw)
         else:
-            ev = pkg.harness.evaluate(run, test_loader, a.batch_size)
+            ev = pkg.harness.evaluate(run, test_loader, a.batch_size, **eval_kw)
         if a.checkpoint is not None:
             # the model a user takes away: the averaged weights when there is an average, in a model-only file
             if a.ema_decay is not None:
@@ -362,6 +385,15 @@ def main(argv=None):
            "final_val_acc": res["final_val_acc"], "final_val_loss": res["final_val_loss"], "test_acc": ev["test_acc"],
            "test_loss": ev["test_loss"], "avg_inference_time_per_image": ev["avg_inference_time_per_image"],
            "peak_gpu_memory_mb": res["peak_gpu_memory_mb"]}
+    if a.eval_topk is not None:
+        row.update({f"test_top{k}": ev[f"test_top{k}"] for k in a.eval_topk})
+        print("Test " + " | ".join(f"top-{k}: {ev[f'test_top{k}']:.2f}%" for k in a.eval_topk))
+    if a.eval_per_class:
+        print("Per-class test accuracy: " + " ".join(f"{v:.1f}" for v in ev["test_per_class_acc"]))
+    if a.eval_confusion is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(a.eval_confusion)), exist_ok=True)
+        np.save(a.eval_confusion, ev["test_confusion"].numpy())
+        print(f"Confusion matrix saved to {a.eval_confusion}")
     if opt.skipped_steps is not None:
         print(f"updates skipped for a non-finite gradient norm: {int(opt.skipped_steps)}")
     path = os.path.join(a.results_dir, f"exp_{a.experiment}.csv")
