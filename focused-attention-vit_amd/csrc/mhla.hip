@@ -16,44 +16,7 @@
 
 namespace {
 
-// closed form of MultiHeadLatentAttention._get_window_indices (mhla.py:46-83)
-__device__ __forceinline__ int win_idx(int i, int w, int L, int W, int h) {
-  const int lo = max(0, i - h), hi = min(L, i + h + 1), n = hi - lo;
-  if (n == W) return lo + w;
-  if (lo == 0) return w < n ? w : L - 1;       // short window starting at 0: pad END with L-1
-  const int pad = W - n;
-  return w < pad ? 0 : lo + (w - pad);         // otherwise: pad FRONT with 0
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void vload(const T* p, float (&o)[N]) {
-  constexpr int BYTES = N * (int)sizeof(T);
-  constexpr int NW = BYTES / 4;
-  uint32_t w[NW];
-  if constexpr (BYTES % 16 == 0) {
-#pragma unroll
-    for (int c = 0; c < BYTES / 16; ++c) {
-      const uint4 u = reinterpret_cast<const uint4*>(p)[c];
-      w[4 * c] = u.x; w[4 * c + 1] = u.y; w[4 * c + 2] = u.z; w[4 * c + 3] = u.w;
-    }
-  } else if constexpr (BYTES == 8) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    w[0] = u.x; w[1] = u.y;
-  } else {
-    static_assert(BYTES == 4, "unsupported vector width");
-    w[0] = *reinterpret_cast<const uint32_t*>(p);
-  }
-  if constexpr (sizeof(T) == 4) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) o[j] = __uint_as_float(w[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < N / 2; ++j) {
-      o[2 * j] = __uint_as_float(w[j] << 16);
-      o[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  }
-}
+// (win_idx, the closed form of the window rule, and vload live in common.h: attn_maps.hip shares them)
 
 template <typename T, int N>
 __device__ __forceinline__ void vstore(T* p, const float (&v)[N]) {

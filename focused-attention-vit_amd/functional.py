@@ -13,6 +13,7 @@ compute-dtype copy that feeds the backward GEMMs.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import weakref
 from collections import namedtuple
@@ -746,6 +747,67 @@ CrossSaved = namedtuple("CrossSaved", "qn kn q k v o w_c att mask B Lq Lk p_attn
 MLPSaved = namedtuple("MLPSaved", "xn pre pre_is_grad h w1_c w2_c p seed_fc1 seed_fc2 prm")
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Attention maps.  kind: "mhla" (probs [B, L, W], or [B, H, L, W] per head, slot layout of
+# window_indices) or "dense" (probs [B, L, L] / [B, H, L, L], W = 0); fp32, in original token coordinates.
+AttentionRecord = namedtuple("AttentionRecord", "kind probs W B L H")
+_CAPTURE = {"active": None}
+
+
+class AttentionCapture:
+    """What capture_attention yields.  layers: one AttentionRecord per attention chain that ran, in execution order."""
+
+    def __init__(self, per_head: bool):
+        self.per_head = bool(per_head)
+        self.layers: List[AttentionRecord] = []
+
+    @staticmethod
+    def admit(who: str, training: bool) -> None:
+        """Raises where a chain's forward cannot be captured: the maps describe the eval forward as stored."""
+        if training:
+            raise RuntimeError(f"capture_attention: {who}.fwd ran in training mode; attention maps are taken from an "
+                               "eval-mode forward (model.eval(), no dropout draws)")
+        if _STATE.get("fp8"):
+            raise RuntimeError("capture_attention: the fp8 compute mode is active; capture in bf16, fp32 or fp32x3")
+
+
+@contextlib.contextmanager
+def capture_attention(per_head: bool = False):
+    """While active, every MHLAChain.fwd / DenseChain.fwd also runs the probability kernel (K.mhla_attn_probs /
+    K.sdpa_probs) on the qkv its projection just wrote -- the values the fused attention kernel reads -- and appends an
+    AttentionRecord to the yielded object's .layers (head-mean maps, or per-head ones with per_head=True).  The
+    unpruned Python chains run: cls_only_cuts returns None and the native block path is not taken, so the maps are in
+    original token coordinates (pruned capture, the compact head + tail layout mapped back, is not implemented).
+    Raises: ValueError for a nested capture; RuntimeError in fp8 mode, for a forward in training mode and for a
+    CrossChain.  With no capture active the chains do one dictionary lookup more and nothing else."""
+    if _CAPTURE["active"] is not None:
+        raise ValueError("capture_attention: a capture is already active; captures do not nest")
+    AttentionCapture.admit("capture_attention", False)
+    cap = AttentionCapture(per_head)
+    _CAPTURE["active"] = cap
+    try:
+        yield cap
+    finally:
+        _CAPTURE["active"] = None
+
+
+def window_indices(L: int, W: int) -> torch.Tensor:
+    """int64 [L, W] on the CPU: the key in slot w of row i of an MHLA window (the closed form of the reference's
+    MultiHeadLatentAttention._get_window_indices, win_idx in csrc/common.h).  A window cut at 0 repeats key L - 1 in
+    its last slots, a window cut at L only repeats key 0 in its first slots."""
+    if W < 1 or W % 2 == 0 or L < 1:
+        raise ValueError(f"window_indices: L >= 1 and an odd W >= 1, got L = {L}, W = {W}")
+    h = W // 2
+    i = torch.arange(L, dtype=torch.int64).unsqueeze(1)
+    w = torch.arange(W, dtype=torch.int64).unsqueeze(0)
+    lo = (i - h).clamp(min=0)
+    n = (i + h + 1).clamp(max=L) - lo
+    pad = W - n
+    at_start = torch.where(w < n, w.expand(L, W), torch.full((L, W), L - 1, dtype=torch.int64))
+    at_end = torch.where(w < pad, torch.zeros((L, W), dtype=torch.int64), lo + w - pad)
+    return torch.where(n == W, lo + w, torch.where(lo == 0, at_start, at_end))
+
+
 class MHLAChain:
     q8_fwd, q8_bwd = 0, 4        # prm index of the weight whose GEMM consumes the chain's input (qkv) / output gradient (proj)
     """MultiHeadLatentAttention.forward (models/mhla.py:85-161)."""
@@ -759,6 +821,9 @@ class MHLAChain:
     def fwd(self, xn, prm, B, L, residual, mask, training, pre=None):
         """mask: [B, L, L] (0 = masked) or None.  pre: (weff, beff) where the caller has folded latent_proj already."""
         _check_mask_shape("MHLAChain", mask, "[B, L, L]", (B, L, L))
+        cap = _CAPTURE["active"]
+        if cap is not None:
+            cap.admit("MHLAChain", training)
         wqkv, bqkv, wl, bl, wp, bp = prm
         M, D = xn.shape
         H, hd = self.H, D // self.H
@@ -768,6 +833,9 @@ class MHLAChain:
         sp = _seed() if pp > 0 else 0
         weff, beff = pre if pre is not None else K.mhla_fold_fwd(wqkv, bqkv, wl, bl, H, xn.dtype)
         qkv = lin_fwd(xn, weff, beff, M, 3 * D, D, xn.dtype, site=wqkv)
+        if cap is not None:
+            cap.layers.append(AttentionRecord("mhla", K.mhla_attn_probs(qkv, B, L, H, hd, self.W, mask,
+                                                                        head_mean=not cap.per_head), self.W, B, L, H))
         # training: the forward also leaves lse per row, and backward runs the saved-statistics kernel (None where
         # that kernel does not apply: other head sizes, fp32)
         o, lse = K.mhla_attn_fwd(qkv, B, L, H, hd, self.W, mask, pa, sa, want_lse=True) if training else \
@@ -851,6 +919,9 @@ class DenseChain:
 
     def fwd(self, xn, prm, B, L, residual, mask, training):
         _check_mask_shape("DenseChain", mask, "key-keep [B, L]", (B, L))
+        cap = _CAPTURE["active"]
+        if cap is not None:
+            cap.admit("DenseChain", training)
         wqkv, bqkv, wp, bp = prm
         M, D = xn.shape
         H, hd = self.H, D // self.H
@@ -860,6 +931,9 @@ class DenseChain:
         sp = _seed() if pp > 0 else 0
         wqkv_c, wp_c = wcast(wqkv), wcast(wp)
         qkv = lin_fwd(xn, wqkv_c, bqkv.detach(), M, 3 * D, D, xn.dtype, site=wqkv)
+        if cap is not None:
+            cap.layers.append(AttentionRecord("dense", K.sdpa_probs(qkv, B, L, H, hd, mask, hd ** -0.5,
+                                                                    head_mean=not cap.per_head), 0, B, L, H))
         o = torch.empty((M, D), dtype=xn.dtype, device=xn.device)
         q, k, v = self._views(qkv, B, L, D, hd)
         ov = _View(o, 0, D, L * D, hd)
@@ -902,6 +976,9 @@ class CrossChain:
 
     def fwd(self, qn, kn, prm, B, Lq, Lk, residual, mask, training):
         _check_mask_shape("CrossChain", mask, "[B, Lq, Lk]", (B, Lq, Lk))
+        if _CAPTURE["active"] is not None:
+            raise RuntimeError("capture_attention: a CrossChain ran under the capture; cross-attention maps (Lq x Lk, "
+                               "two sequences) are not implemented")
         wq, bq, wk, bk, wv, bv, wo, bo = prm
         D = qn.shape[1]
         H, hd = self.H, D // self.H
@@ -1184,8 +1261,11 @@ def cls_only_cuts(specs: Sequence["BlockSpec"], L: int, mask, training: bool):
     that is not MHLA + MLP, differing windows, an attention mask, a dropout that is active in this mode (the masks are
     indexed by element position: a compact layout would draw other masks), fp8 mode (its quantisation sites hand
     tensors of the full shape from kernel to kernel), FAVIT_NO_PRUNE=1 (A/B switch, read at each call), or a sequence
-    so short that every block needs all rows."""
+    so short that every block needs all rows, or an active capture_attention (its maps are in original token
+    coordinates)."""
     if os.environ.get("FAVIT_NO_PRUNE") or mask is not None or not specs or _STATE.get("fp8"):
+        return None
+    if _CAPTURE["active"] is not None:
         return None
     if not all(isinstance(s.attn, MHLAChain) and isinstance(s.mlp, MLPChain) for s in specs):
         return None
@@ -1236,8 +1316,8 @@ def set_native_blocks(on: bool) -> None:
 
 def _native_blocks_on() -> bool:
     """The conditions that do not depend on the block.  K.GEMM_TRACE has to see every GEMM; the side stream is a
-    launch pattern of the Python chains only."""
-    return (_NATIVE["on"] and K.GEMM_TRACE is None and not _SIDE["enabled"]
+    launch pattern of the Python chains only; capture_attention hooks the Python chains' qkv."""
+    return (_NATIVE["on"] and K.GEMM_TRACE is None and not _SIDE["enabled"] and _CAPTURE["active"] is None
             and get_compute_mode() == "bf16" and not os.environ.get("FAVIT_NO_NATIVE_BLOCKS"))
 
 

@@ -15,6 +15,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from . import functional as F
 from . import kernels as K
 from . import train as T
 from .data import MixedLabels
@@ -329,6 +330,55 @@ def evaluate(model, loader: Iterable, batch_size: Optional[int] = None, metrics:
     bs = batch_size or max(1, total // n_batches)
     return {"test_loss": loss_sum.item() / n_batches, "test_acc": 100.0 * correct.item() / max(1, total),
             "avg_inference_time": infer_s / n_batches, "avg_inference_time_per_image": infer_s / n_batches / bs}
+
+
+def _cls_row_per_key(rec, probs) -> torch.Tensor:
+    """[B, L]: row 0 of a head-mean map, the slots of a banded map summed per key."""
+    if rec.kind == "dense":
+        return probs[:, 0, :].clone()
+    idx = F.window_indices(rec.L, rec.W)[0].to(probs.device)
+    return torch.zeros((rec.B, rec.L), dtype=torch.float32, device=probs.device).index_add_(1, idx, probs[:, 0, :])
+
+
+def attention_maps(model, images: torch.Tensor, per_head: bool = False, residual: float = 0.5) -> Dict[str, object]:
+    """Where the CLS row of `model` looks for `images`: one eval-mode forward under torch.no_grad() and
+    functional.capture_attention (the unpruned Python chains, with the probability kernel on every block's stored
+    qkv), then attention rollout of row 0 through all blocks in one launch (K.attn_rollout).  The model's `training`
+    flag is restored.  Returns
+      logits         the forward's output
+      rollout        fp32 [B, L]: r = e_0, and from the last block to the first r <- residual r + (1 - residual) r P_k
+                     with P_k the block's head-mean map
+      cls_attention  fp32 [B, L]: the last block's CLS row, head mean, slots summed per key
+      layers         the blocks' maps in order: head-mean [B, L, W] (MHLA; slot w of row i is key
+                     functional.window_indices(L, W)[i, w]) or [B, L, L] (dense); with per_head the per-head maps
+                     [B, H, L, W] / [B, H, L, L] (rollout then uses their mean over the heads)
+      window         per block its W, 0 for a dense block
+      grid           fp32 [B, gh, gw], for models with a patch_embed: rollout[:, 1:] on the patch grid; for a superpixel
+                     model every patch gets the value of the token its superpixel became; None for other models."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), F.capture_attention(per_head=per_head) as cap:
+            logits = model(images)
+    finally:
+        model.train(was_training)
+    if not cap.layers:
+        raise RuntimeError("attention_maps: the model ran no MHLA or dense attention chain")
+    means = [r.probs.mean(dim=1) if per_head else r.probs for r in cap.layers]
+    window = [r.W for r in cap.layers]
+    rollout = K.attn_rollout(means, window, cls_row=0, residual=residual)
+    out = {"logits": logits, "rollout": rollout, "cls_attention": _cls_row_per_key(cap.layers[-1], means[-1]),
+           "layers": [r.probs for r in cap.layers], "window": window, "grid": None}
+    pe = getattr(model, "patch_embed", None)
+    if pe is not None and hasattr(pe, "patch_size") and images.dim() == 4:
+        B = images.shape[0]
+        gh, gw = images.shape[2] // pe.patch_size, images.shape[3] // pe.patch_size
+        if hasattr(model, "patch_mapper"):        # patch p of image b was pooled into token 1 + rank[b, p] (sppp_tokens)
+            rank = model.patch_mapper.map_patches_batched(model.segmentation.segment(images).to(images.device))[0]
+            out["grid"] = rollout[:, 1:].gather(1, rank.long()).reshape(B, gh, gw)
+        elif rollout.shape[1] == gh * gw + 1:
+            out["grid"] = rollout[:, 1:].reshape(B, gh, gw).clone()
+    return out
 
 
 def fit(model, train_loader: Iterable, val_loader: Optional[Iterable], optimizer, epochs: int,

@@ -1268,6 +1268,86 @@ def eval_metrics(logits, labels, state, loss_rows, pred_rows, rank_rows, topk=(1
                                              len(ks), k4[0], k4[1], k4[2], k4[3], _st()), "favit_eval_metrics")
 
 
+MAPS_MAX_WINDOW = _abi.MAPS_MAX_WINDOW
+ROLLOUT_MAX_LAYERS = _abi.ROLLOUT_MAX_LAYERS
+ROLLOUT_MAX_L = _abi.ROLLOUT_MAX_L
+
+
+def _check_qkv(who, qkv, B, L, H, hd):
+    if not torch.is_tensor(qkv) or qkv.dim() != 2 or tuple(qkv.shape) != (B * L, 3 * H * hd) \
+            or not qkv.is_contiguous() or qkv.dtype not in _DT:
+        got = f"{qkv.dtype} {tuple(qkv.shape)}" if torch.is_tensor(qkv) else type(qkv).__name__
+        raise ValueError(f"{who}: qkv must be a contiguous fp32 or bf16 [B*L, 3*H*hd] = ({B * L}, {3 * H * hd}) "
+                         f"tensor, got {got}")
+
+
+def mhla_attn_probs(qkv, B, L, H, hd, W, mask=None, head_mean=False):
+    """favit_mhla_attn_probs: the window probabilities of mhla_attn_fwd's softmax, recomputed from the stored qkv
+    [B*L, 3*H*hd].  fp32 [B, H, L, W], or [B, L, W] with head_mean (heads summed in ascending order, times 1 / H).
+    Slot w of row i is key functional.window_indices(L, W)[i, w]; pad copies are slots of their own.  mask as in
+    mhla_attn_fwd: masked slots are exactly 0 and a row without a live slot is all zeros."""
+    _check_qkv("mhla_attn_probs", qkv, B, L, H, hd)
+    if W < 1 or W % 2 == 0:
+        raise ValueError(f"mhla_attn_probs: the window must be odd and positive, got W = {W}")
+    _check_mhla_mask(mask, qkv, B, L)
+    require_gpu(qkv, mask)
+    probs = torch.empty((B, L, W) if head_mean else (B, H, L, W), dtype=torch.float32, device=qkv.device)
+    _abi.check(_abi.lib().favit_mhla_attn_probs(_p(qkv), _p(probs), _p(mask), B, L, H, hd, W, dt(qkv),
+                                                1 if head_mean else 0, _st()), "favit_mhla_attn_probs")
+    return probs
+
+
+def sdpa_probs(qkv, B, L, H, hd, key_keep=None, scale=None, head_mean=False):
+    """favit_sdpa_probs: softmax(scale * q k^T) of the dense self-attention on qkv [B*L, 3*H*hd] (q, k = column blocks
+    0 and D, DenseChain's layout).  fp32 [B, H, L, L], or [B, L, L] with head_mean.  key_keep: contiguous uint8 / bool
+    [B, L] (0 masks the key) or None; scale defaults to hd ** -0.5."""
+    _check_qkv("sdpa_probs", qkv, B, L, H, hd)
+    if key_keep is not None and tuple(key_keep.shape) != (B, L):
+        raise ValueError(f"sdpa_probs: key_keep must have shape ({B}, {L}), got {tuple(key_keep.shape)}")
+    _check_dense_mask("sdpa_probs", key_keep, L, 0, B, L, L)
+    require_gpu(qkv, key_keep)
+    probs = torch.empty((B, L, L) if head_mean else (B, H, L, L), dtype=torch.float32, device=qkv.device)
+    _abi.check(_abi.lib().favit_sdpa_probs(_p(qkv), _p(probs), _p(key_keep), B, L, H, hd, dt(qkv),
+                                           float(hd ** -0.5 if scale is None else scale), 1 if head_mean else 0, _st()),
+               "favit_sdpa_probs")
+    return probs
+
+
+def attn_rollout(probs, widths, cls_row=0, residual=0.5):
+    """favit_attn_rollout: attention rollout of the row cls_row through a stack of head-mean maps, one launch.
+    probs[k]: block k's map, contiguous fp32 [B, L, W_k] (widths[k] = W_k, odd) or [B, L, L] (widths[k] = 0, dense), in
+    block order, at most ROLLOUT_MAX_LAYERS of them; L <= ROLLOUT_MAX_L.  Returns fp32 [B, L]: r = e_cls_row, and from
+    the last block to the first r <- residual * r + (1 - residual) * r P_k.  Bitwise reproducible."""
+    probs, widths = list(probs), [int(w) for w in widths]
+    n = len(probs)
+    if not 1 <= n <= ROLLOUT_MAX_LAYERS or len(widths) != n:
+        raise ValueError(f"attn_rollout: 1..{ROLLOUT_MAX_LAYERS} maps with one width each, got {n} maps and "
+                         f"{len(widths)} widths")
+    if not torch.is_tensor(probs[0]) or probs[0].dim() != 3:
+        raise ValueError("attn_rollout: every map must be a [B, L, W] or [B, L, L] tensor")
+    B, L = probs[0].shape[:2]
+    for k, (p, w) in enumerate(zip(probs, widths)):
+        if w < 0 or (w > 0 and w % 2 == 0):
+            raise ValueError(f"attn_rollout: widths[{k}] = {w} is neither 0 (dense) nor an odd window")
+        want = (B, L, w if w > 0 else L)
+        if not torch.is_tensor(p) or p.dtype != torch.float32 or tuple(p.shape) != want or not p.is_contiguous():
+            got = f"{p.dtype} {tuple(p.shape)}" if torch.is_tensor(p) else type(p).__name__
+            raise ValueError(f"attn_rollout: map {k} must be a contiguous fp32 tensor of shape {want}, got {got}")
+    if not 0 <= cls_row < L:
+        raise ValueError(f"attn_rollout: cls_row = {cls_row} outside [0, {L})")
+    if not 0.0 <= residual <= 1.0:
+        raise ValueError(f"attn_rollout: residual = {residual} outside [0, 1]")
+    if L > ROLLOUT_MAX_L:
+        raise ValueError(f"attn_rollout: L = {L} exceeds ROLLOUT_MAX_L = {ROLLOUT_MAX_L} (two rows of L floats in LDS)")
+    require_gpu(*probs)
+    out = torch.empty((B, L), dtype=torch.float32, device=probs[0].device)
+    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in probs])
+    ws = (C.c_int32 * n)(*widths)
+    _abi.check(_abi.lib().favit_attn_rollout(n, ptrs, ws, _p(out), cls_row, B, L, float(residual), _st()),
+               "favit_attn_rollout")
+    return out
+
+
 GRAD_NORM_MAX_BUFS = _abi.GRAD_NORM_MAX_BUFS
 
 

@@ -860,6 +860,56 @@ int favit_eval_metrics(const float* logits, int64_t ld, const int64_t* labels, f
                        int64_t* class_correct /* [C] or NULL */, int64_t* confusion /* [C * C] or NULL */, int32_t B,
                        int32_t C, int32_t n_topk, int32_t k0, int32_t k1, int32_t k2, int32_t k3, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Attention maps (additive in ABI 8; csrc/attn_maps.hip): the probabilities that the fused
+ * attention kernels never write, recomputed from the qkv a forward stored, and attention rollout (Abnar and Zuidema)
+ * over a stack of head-mean maps.  Diagnostics: no backward, no dropout; every output is fp32.
+ * ---------------------------------------------------------------------------------- */
+#define FAVIT_MAPS_MAX_WINDOW 15              /* largest window of favit_mhla_attn_probs */
+#define FAVIT_SDPA_PROBS_MAX_WAVE_FLOATS 4096 /* favit_sdpa_probs: H * hd + 2 * H may not exceed this (LDS per wave) */
+#define FAVIT_ROLLOUT_MAX_LAYERS 32           /* blocks per favit_attn_rollout launch */
+#define FAVIT_ROLLOUT_MAX_L 16384             /* tokens per image in favit_attn_rollout: two fp32 rows of L in LDS */
+/* Window probabilities of the MHLA core.  qkv: the folded projection output [B*L, 3D] of the attention forward above
+ * (column = s*D + h*hd + d, D = H*hd), fp32 or bf16 (dtype), 16-byte aligned.  Slot w of row i is the key
+ * win_idx(i, w) of the window rule (csrc/common.h; the table functional.window_indices returns): pad copies are slots
+ * of their own, as in the forward, and a key's total weight is the sum of its slots.  Scores q . k~ / sqrt(hd) are
+ * accumulated in fp32 and the softmax runs over the W slots of the row.
+ *   head_mean = 0: probs fp32 [B, H, L, W];  head_mean = 1: probs fp32 [B, L, W], the probabilities of the heads
+ *   summed in ascending head order in fp32, then multiplied by 1 / H.
+ * mask: as in the forward (uint8 [B, L, L], non-zero keeps the key, NULL = none), and its contract: a masked slot of a
+ * live row is exactly 0, a row whose slots are all masked is all zeros, nothing non-finite is written for finite qkv.
+ * Runs for odd W <= FAVIT_MAPS_MAX_WINDOW, hd in {16, 32, 64, 128}, any L >= 1 (L < W included), one launch, eight
+ * lanes per token row.  Even or non-positive W, a NULL qkv / probs, B, L, H < 1, another dtype or head_mean outside
+ * {0, 1}: FAVIT_ERR_INVALID; another W or hd, or B*L >= 2^28: FAVIT_ERR_UNSUPPORTED; a misaligned qkv:
+ * FAVIT_ERR_ALIGN.  Nothing is launched or written then. */
+int favit_mhla_attn_probs(const void* qkv, float* probs, const uint8_t* mask, int32_t B, int32_t L, int32_t H,
+                          int32_t hd, int32_t W, int dtype, int32_t head_mean, void* stream);
+/* The dense counterpart: softmax(scale * q k^T) of the self-attention whose q and k are the column blocks 0 and D of
+ * qkv [B*L, 3D] (fp32 or bf16, 16-byte aligned).  key_keep: uint8 [B, L] (0 masks the key for every query of the
+ * sample) or NULL.  probs: fp32 [B, H, L, L] (head_mean = 0) or [B, L, L] (head_mean = 1, ascending head order, then
+ * 1 / H).  A masked key has probability exactly 0 and a sample whose keys are all masked has all-zero rows.  One wave
+ * per query row; hd % 16 == 0, H*hd + 2*H <= FAVIT_SDPA_PROBS_MAX_WAVE_FLOATS (else FAVIT_ERR_UNSUPPORTED), any
+ * L >= 1; scale must be finite and > 0 (else FAVIT_ERR_INVALID, as for the arguments listed above). */
+int favit_sdpa_probs(const void* qkv, float* probs, const uint8_t* key_keep, int32_t B, int32_t L, int32_t H,
+                     int32_t hd, int dtype, float scale, int32_t head_mean, void* stream);
+/* Attention rollout of n blocks (1 <= n <= FAVIT_ROLLOUT_MAX_LAYERS) in ONE launch.  probs / widths: HOST arrays of n
+ * entries in block order; probs[k] is block k's head-mean map on the device, fp32 [B, L, W_k] in the slot layout above
+ * where widths[k] = W_k is odd and > 0, or fp32 [B, L, L] where widths[k] = 0 (a dense block); the two kinds may mix.
+ * In row-vector form, r = e_cls_row, and for k = n-1 .. 0:
+ *   r'[j] = residual * r[j] + (1 - residual) * sum_i r[i] * P_k[i -> j]          out fp32 [B, L] = the last r
+ * (P_k[i -> j] of a banded block: the sum of the slots of row i that hold key j).  0 <= residual <= 1.
+ * One workgroup per image keeps r in LDS as two rows of L floats that swap after every block, so L is bounded by LDS
+ * alone: L <= FAVIT_ROLLOUT_MAX_L (128 KiB of the CU's 160; FAVIT_ERR_UNSUPPORTED beyond).  Every key j GATHERS its
+ * sources in a fixed order -- the rows j - W/2 .. j + W/2 whose window holds j, ascending; for j = L - 1 then the pad
+ * copies of the short windows that start at 0; for j = 0 the pad copies of the windows cut at L; a dense block sums
+ * the rows in ascending order -- so there are no atomics and the same inputs give the same bits in every run.
+ * A row of P_k that is all zero (a fully masked row) hands nothing on: the mass r[i] that reached it is lost except
+ * for its residual share, and out then sums to less than 1.
+ * FAVIT_ERR_INVALID before any launch: NULL probs, widths, out or probs[k]; n, B, L < 1; n above the limit; cls_row
+ * outside [0, L); an even or negative widths[k]; residual outside [0, 1] or NaN. */
+int favit_attn_rollout(int32_t n, const float* const* probs, const int32_t* widths, float* out, int32_t cls_row,
+                       int32_t B, int32_t L, float residual, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
