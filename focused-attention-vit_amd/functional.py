@@ -14,6 +14,7 @@ compute-dtype copy that feeds the backward GEMMs.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 import weakref
 from collections import namedtuple
@@ -1196,27 +1197,80 @@ class PatchEmbedOp:
         return [dimg], [dw, db]
 
 
-class PrologueOp:
-    """cat(cls, tokens) (+ pos_embed) (models/vit.py:292-296, models/sppp_mhla.py:303-304)."""
+pos_resample_matrix = K.pos_resample_matrix
 
-    def __init__(self, has_pos):
-        self.has_pos = has_pos
+
+def _grid_side(n: int) -> Optional[int]:
+    """g with g * g == n, or None."""
+    g = math.isqrt(n) if n >= 1 else 0
+    return g if g >= 1 and g * g == n else None
+
+
+class _PosResampleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, g_in, g_out, antialias, n_prefix):
+        K.require_gpu(pos)
+        ctx.cfg = (g_in, g_out, antialias, n_prefix, pos.shape)
+        x = _as_f32(pos.detach()).reshape(-1, pos.shape[-1]).contiguous()
+        y = K.pos_resample(x, g_in, g_out, antialias, n_prefix)
+        return y.reshape(*pos.shape[:-2], y.shape[0], y.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        g_in, g_out, antialias, n_prefix, shape = ctx.cfg
+        d = _as_f32(dy).reshape(-1, shape[-1]).contiguous()
+        return K.pos_resample(d, g_in, g_out, antialias, n_prefix, adjoint=True).reshape(shape), None, None, None, None
+
+
+def pos_resample(pos: torch.Tensor, g_out: int, antialias: bool = True, n_prefix: int = 1) -> torch.Tensor:
+    """A learned position embedding on a square grid, resampled to a g_out x g_out grid on the device (bicubic,
+    align_corners=False; antialias as in pos_resample_matrix, True being timm's default).  pos: fp32
+    [n_prefix + g_in^2, D] or [1, n_prefix + g_in^2, D] on the GPU; the n_prefix (0 or 1) leading rows -- the CLS row
+    -- are copied.  Forward and backward are one favit_pos_resample launch each (the backward with the transposed
+    table: the exact adjoint, no atomics, bitwise reproducible); the gradient has pos's shape.  D % 4 == 0."""
+    if pos.dim() not in (2, 3) or (pos.dim() == 3 and pos.shape[0] != 1):
+        raise ValueError(f"pos_resample: pos must be [n, D] or [1, n, D], got {tuple(pos.shape)}")
+    g_in = _grid_side(pos.shape[-2] - n_prefix)
+    if g_in is None:
+        raise ValueError(f"pos_resample: {pos.shape[-2] - n_prefix} grid rows (of {pos.shape[-2]} with {n_prefix} prefix "
+                         "rows) are not a square grid")
+    return _PosResampleFn.apply(pos, g_in, int(g_out), bool(antialias), int(n_prefix))
+
+
+class PrologueOp:
+    """cat(cls, tokens) (+ pos_embed) (models/vit.py:292-296, models/sppp_mhla.py:303-304).  A pos_embed whose grid is
+    not the tokens' (an input of another resolution than the parameter was made for) is resampled to the tokens' grid in
+    front of the kernel and its gradient goes back through the adjoint, so the parameter keeps its shape
+    (K.pos_resample, antialias as given).  With equal grids nothing of that runs."""
+
+    def __init__(self, has_pos, antialias=True):
+        self.has_pos, self.antialias = has_pos, bool(antialias)
 
     def fwd(self, ins, prm):
         (tok,) = ins
         cls = prm[0]
         pos = prm[1] if self.has_pos else None
         B, N, D = tok.shape
-        x = K.embed_prologue_fwd(_as_f32(tok), cls.detach().contiguous(), None if pos is None else pos.detach().contiguous(),
-                                 B, N, D)
-        return x, (B, N, D)
+        grids = None
+        if pos is not None:
+            pos = pos.detach().contiguous()
+            if pos.shape[1] != N + 1:
+                grids = (_grid_side(pos.shape[1] - 1), _grid_side(N))
+                if None in grids:
+                    raise ValueError(f"the input gives {N} patch tokens and pos_embed holds {pos.shape[1] - 1} grid rows: "
+                                     "resampling needs both to be perfect squares (a square image, a square pos_embed)")
+                pos = K.pos_resample(_as_f32(pos).reshape(-1, D), grids[0], grids[1], self.antialias)
+        x = K.embed_prologue_fwd(_as_f32(tok), cls.detach().contiguous(), pos, B, N, D)
+        return x, (B, N, D, grids)
 
     def bwd(self, saved, dy, needs):
-        B, N, D = saved
+        B, N, D, grids = saved
         dtok, dcls, dpos = K.embed_prologue_bwd(dy, B, N, D, torch.float32, want_pos=self.has_pos)
         out = [dcls.reshape(1, 1, D)]
         if self.has_pos:
-            out.append(dpos.reshape(1, N + 1, D))
+            if grids is not None:
+                dpos = K.pos_resample(dpos, grids[0], grids[1], self.antialias, adjoint=True)
+            out.append(dpos.reshape(1, -1, D))
         return [dtok.reshape(B, N, D)], out
 
 

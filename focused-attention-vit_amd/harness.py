@@ -190,6 +190,8 @@ class GraphedEval:
       copies made during warm-up are kept alive with this object, and after editing weights a new GraphedEval is needed.
     * SPPP models need ``assume_num_tokens`` and installed label maps, as GraphedStep does, and full batches (the label
       maps have the captured batch size).
+    * One resolution per capture: at an image size other than the model's own the graph holds the pos_embed
+      resampling launch (functional.PrologueOp), whose table the warm-up runs upload; another size is another object.
     * The metrics' state is left as found by construction (warm-up runs are undone)."""
 
     def __init__(self, model: torch.nn.Module, images: torch.Tensor, labels: torch.Tensor, metrics: EvalMetrics,

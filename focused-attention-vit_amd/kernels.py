@@ -1348,6 +1348,107 @@ def attn_rollout(probs, widths, cls_row=0, residual=0.5):
     return out
 
 
+POS_RESAMPLE_MAX_L = _abi.POS_RESAMPLE_MAX_L
+
+
+def _cubic(x, a):
+    x = abs(x)
+    if x <= 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    if x < 2.0:
+        return a * (((x - 5.0) * x + 8.0) * x - 4.0)
+    return 0.0
+
+
+def pos_resample_matrix(g_in: int, g_out: int, antialias: bool = True) -> torch.Tensor:
+    """The float64 matrix M [g_out, g_in] of one axis of the bicubic resampling of a grid side g_in to g_out
+    (align_corners=False): resampling a g_in x g_in grid X is M X M^T.  antialias=False is torch's plain bicubic
+    (a = -0.75, four taps at floor(src) - 1 .. + 2, indices clamped to the grid and accumulated); antialias=True is
+    torch's and Pillow's antialiased bicubic (a = -0.5, support 2 * max(scale, 1), weights normalised to sum to 1),
+    timm's default for position embeddings.  Equal sides give the identity exactly.  Built in Python floats."""
+    g_in, g_out = int(g_in), int(g_out)
+    if g_in < 1 or g_out < 1:
+        raise ValueError(f"pos_resample_matrix: grid sides must be >= 1, got {g_in} -> {g_out}")
+    M = np.zeros((g_out, g_in), dtype=np.float64)
+    scale = g_in / g_out
+    for d in range(g_out):
+        if antialias:
+            support, inv, center = 2.0 * max(scale, 1.0), 1.0 / max(scale, 1.0), scale * (d + 0.5)
+            xmin, xmax = max(int(center - support + 0.5), 0), min(int(center + support + 0.5), g_in)
+            w = [_cubic((j + xmin - center + 0.5) * inv, -0.5) for j in range(xmax - xmin)]
+            tot = sum(w)
+            for j, v in enumerate(w):
+                M[d, xmin + j] = v / tot
+        else:
+            src = (d + 0.5) * scale - 0.5
+            f = math.floor(src)
+            t = src - f
+            for k in range(-1, 3):
+                M[d, min(max(f + k, 0), g_in - 1)] += _cubic(k - t, -0.75)
+    return torch.from_numpy(M)
+
+
+def _csr(M32: np.ndarray):
+    """(rowptr int32, cols int32, vals fp32) of the non-zero entries of a 2-D fp32 matrix, columns ascending."""
+    rows, cols = np.nonzero(M32)                               # row-major order: rows ascending, then columns
+    rowptr = np.zeros(M32.shape[0] + 1, dtype=np.int32)
+    np.cumsum(np.bincount(rows, minlength=M32.shape[0]), out=rowptr[1:])
+    return rowptr, cols.astype(np.int32), np.ascontiguousarray(M32[rows, cols], dtype=np.float32)
+
+
+_POS_TABLES = {}          # (device index, g_in, g_out, antialias) -> ((rowptr, cols, vals) of M, the same of M^T)
+
+
+def pos_resample_tables(g_in: int, g_out: int, antialias: bool, device):
+    """The device tables favit_pos_resample reads for (g_in -> g_out, antialias): the compressed rows of
+    pos_resample_matrix rounded to fp32, and those of its transpose (the adjoint's table: the same fp32 values).  Built,
+    checked and uploaded ONCE per device and kept, so that a later call -- inside a HIP graph capture too -- allocates
+    and copies nothing; the eager warm-up steps of GraphedStep / GraphedEval fill the cache."""
+    dev = torch.device(device)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), int(g_in), int(g_out), bool(antialias))
+    hit = _POS_TABLES.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"pos_resample: no table for {g_in} -> {g_out} on this device yet, and a HIP graph is being "
+                               "captured (an upload cannot be captured): run one eager step at this resolution first")
+        M32 = pos_resample_matrix(g_in, g_out, antialias).numpy().astype(np.float32)
+        both = []
+        for mat, n_cols in ((M32, g_in), (np.ascontiguousarray(M32.T), g_out)):
+            rowptr, cols, vals = _csr(mat)
+            if rowptr[0] != 0 or np.any(np.diff(rowptr) < 0) or rowptr[-1] != len(cols) or len(cols) != len(vals) \
+                    or cols.min() < 0 or cols.max() >= n_cols:
+                raise AssertionError(f"pos_resample: malformed table for {g_in} -> {g_out}")
+            both.append(tuple(torch.from_numpy(t).to(dev) for t in (rowptr, cols, vals)))
+        hit = _POS_TABLES[key] = tuple(both)
+    return hit
+
+
+def pos_resample(x, g_in: int, g_out: int, antialias: bool = True, n_prefix: int = 1, adjoint: bool = False):
+    """favit_pos_resample.  x: contiguous fp32 [n_prefix + g_in^2, D] -> [n_prefix + g_out^2, D]: the n_prefix leading
+    rows copied, the grid rows resampled with M = pos_resample_matrix(g_in, g_out, antialias) along both axes.
+    adjoint=True applies the transpose instead (the backward): x is [n_prefix + g_out^2, D], the result
+    [n_prefix + g_in^2, D].  One launch, no atomics, bitwise reproducible; D % 4 == 0."""
+    g_in, g_out, n_prefix = int(g_in), int(g_out), int(n_prefix)
+    g_src, g_dst = (g_out, g_in) if adjoint else (g_in, g_out)
+    if n_prefix not in (0, 1):
+        raise ValueError(f"pos_resample: n_prefix must be 0 or 1, got {n_prefix}")
+    if g_in < 1 or g_out < 1 or max(g_in, g_out) ** 2 + n_prefix > POS_RESAMPLE_MAX_L:
+        raise ValueError(f"pos_resample: grid sides {g_in} -> {g_out} outside 1 .. {POS_RESAMPLE_MAX_L} token rows")
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() \
+            or x.shape[0] != n_prefix + g_src * g_src:
+        got = f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else type(x).__name__
+        raise ValueError(f"pos_resample: x must be a contiguous fp32 [{n_prefix + g_src * g_src}, D] tensor, got {got}")
+    D = x.shape[1]
+    if D < 4 or D % 4:
+        raise ValueError(f"pos_resample: D = {D} must be a positive multiple of 4")
+    require_gpu(x)
+    rowptr, cols, vals = pos_resample_tables(g_in, g_out, antialias, x.device)[1 if adjoint else 0]
+    y = torch.empty((n_prefix + g_dst * g_dst, D), dtype=torch.float32, device=x.device)
+    _abi.check(_abi.lib().favit_pos_resample(_p(x), _p(y), _p(rowptr), _p(cols), _p(vals), g_src, g_dst, n_prefix, D,
+                                             _st()), "favit_pos_resample")
+    return y
+
+
 GRAD_NORM_MAX_BUFS = _abi.GRAD_NORM_MAX_BUFS
 
 

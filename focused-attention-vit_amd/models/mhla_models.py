@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F
-from .vit import PatchEmbedding, embed_dropout, run_encoder, set_drop_path_rate
+from .vit import PatchEmbedding, embed_dropout, run_encoder, set_drop_path_rate, set_pos_antialias
 from .sppp import (SuperpixelSegmentation, PatchToSuperpixelMapper, SuperpixelPooling, DynamicPositionalEncoding,
                    calculate_superpixel_centroids, sppp_tokens)
 from .mhla import MHLATransformerBlock
@@ -44,6 +44,7 @@ class PretrainedViTWithMHLA(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, embed_dim))
+        self.pos_antialias = True              # resampling rule at another input resolution (set_pos_antialias)
         self.pos_drop = nn.Dropout(embed_dropout)
         self.blocks = nn.ModuleList([
             MHLATransformerBlock(embed_dim=embed_dim, num_heads=num_heads, window_size=window_size,
@@ -57,7 +58,7 @@ class PretrainedViTWithMHLA(nn.Module):
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         tok = self.patch_embed(x)
-        x = F.run(F.PrologueOp(True), [tok], [self.cls_token, self.pos_embed])
+        x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
         # only the CLS row is read below: the blocks compute just the rows it can see (functional.cls_plan)
         x = run_encoder(self.blocks, x, None, self.training,
@@ -71,6 +72,7 @@ class PretrainedViTWithMHLA(nn.Module):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     set_drop_path_rate = set_drop_path_rate
+    set_pos_antialias = set_pos_antialias
 
 
 class PretrainedSPPPViTWithMHLA(nn.Module):

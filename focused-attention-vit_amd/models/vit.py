@@ -124,6 +124,15 @@ def set_drop_path_rate(model, drop_path_rate: float = 0.0):
     return model
 
 
+def set_pos_antialias(model, antialias: bool = True):
+    """How a model with a learned grid `pos_embed` resamples it when the input's patch grid is not the parameter's
+    (functional.PrologueOp): antialiased bicubic (True, the default, timm's rule) or torch's plain bicubic (False).
+    A plain attribute `pos_antialias`, handled like drop_path: no parameter, no buffer, no state_dict key.  Returns
+    the model."""
+    model.pos_antialias = bool(antialias)
+    return model
+
+
 def run_encoder(blocks, x, mask, training, cls_only=False):
     """All blocks of a model as ONE autograd node (no per-block fp32<->bf16 gradient casts) -- or, while
     functional.encoder_segments(n) is active (train.GraphedStep with backward segments), as n consecutive nodes cut
@@ -179,6 +188,7 @@ class VisionTransformer(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, embed_dim))
+        self.pos_antialias = True              # resampling rule at another input resolution (set_pos_antialias)
         self.pos_drop = nn.Dropout(embed_dropout)
         self.blocks = nn.ModuleList([
             TransformerBlock(embed_dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, dropout=dropout,
@@ -203,7 +213,7 @@ class VisionTransformer(nn.Module):
 
     def forward_features(self, x):
         tok = self.patch_embed(x)
-        x = F.run(F.PrologueOp(True), [tok], [self.cls_token, self.pos_embed])
+        x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
         x = run_encoder(self.blocks, x, None, self.training)
         return F.run(F.FinalNormOp(), [x], [self.norm.weight, self.norm.bias])
@@ -216,3 +226,4 @@ class VisionTransformer(nn.Module):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     set_drop_path_rate = set_drop_path_rate
+    set_pos_antialias = set_pos_antialias

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F, params
-from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder, set_drop_path_rate
+from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder, set_drop_path_rate, set_pos_antialias
 from .mhla import MultiHeadLatentAttention
 
 
@@ -63,6 +63,7 @@ class VisionTransformerMHLA(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, embed_dim))
+        self.pos_antialias = True              # resampling rule at another input resolution (set_pos_antialias)
         self.pos_drop = nn.Dropout(embed_dropout)
         self.blocks = nn.ModuleList([
             TransformerBlock(embed_dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, dropout=dropout,
@@ -88,7 +89,7 @@ class VisionTransformerMHLA(nn.Module):
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         tok = self.patch_embed(x)
-        x = F.run(F.PrologueOp(True), [tok], [self.cls_token, self.pos_embed])
+        x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
         # only the CLS row is read below: MHLA stacks compute just the rows it can see (functional.cls_plan)
         x = run_encoder(self.blocks, x, None, self.training,
@@ -103,3 +104,4 @@ class VisionTransformerMHLA(nn.Module):
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     set_drop_path_rate = set_drop_path_rate
+    set_pos_antialias = set_pos_antialias

@@ -895,6 +895,9 @@ class GraphedStep:
 
     Requirements: FusedAdamW (its bf16 weight mirror is refreshed by kernels, not by host-side caching), fixed shapes,
     and for SPPP models ``model.assume_num_tokens`` set (the per-forward token-count check is a host sync).
+    Fixed shapes include the image size: a step is ONE resolution per capture.  At a resolution other than the model's
+    own the captured graphs hold the two pos_embed resampling launches (functional.PrologueOp); their tables are
+    uploaded by the eager warm-up steps.  Progressive resizing builds one GraphedStep per size.
 
     * Mixed batches (data.BatchMix): the target weights change every step, so they cannot be a by-value argument.  With
       ``mix=True`` the step owns a static fp32 [B] buffer that the captured loss kernel (favit_cross_entropy_mix) reads

@@ -910,6 +910,29 @@ int favit_sdpa_probs(const void* qkv, float* probs, const uint8_t* key_keep, int
 int favit_attn_rollout(int32_t n, const float* const* probs, const int32_t* widths, float* out, int32_t cls_row,
                        int32_t B, int32_t L, float residual, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Position-embedding resampling (additive in ABI 8; csrc/pos_resample.hip): a square grid of
+ * fp32 token rows, separably resampled to another grid side.  x: fp32 [n_prefix + g_in^2, D], y: fp32
+ * [n_prefix + g_out^2, D], both contiguous and 16-byte aligned, D % 4 == 0, n_prefix 0 or 1 (the CLS row).
+ *   y[p, :] = x[p, :]                                                          for p < n_prefix
+ *   y[n_prefix + a*g_out + b, :] = sum_i sum_j M[a,i] * M[b,j] * x[n_prefix + i*g_in + j, :]
+ * M [g_out, g_in] comes in compressed-row form, DEVICE arrays built by the caller: rowptr int32 [g_out + 1]
+ * (ascending, rowptr[0] = 0), cols int32 [rowptr[g_out]] with every entry in [0, g_in), vals fp32 of the same length.
+ * The kernel trusts the table (focused-attention-vit_amd/kernels.py builds it on the host in float64 -- bicubic with
+ * or without antialiasing, functional.pos_resample_matrix -- checks it, uploads it once and caches it per device).
+ * The products (M[a,i] * M[b,j]) * x are accumulated in fp32 with fused multiply-adds in table order, i outer, j inner.
+ * BOTH DIRECTIONS are this one entry point: the backward of y = R x is dx = R^T dy, the same operation with the
+ * compressed rows of M^T and the two grid sides swapped (prefix rows are copied in both).  It is a gather, one thread
+ * per four columns of an output row: no atomics, the same inputs give the same bits in every run.  A row of M whose
+ * only entry is 1 copies its source row bit for bit (an identity M is a copy).  One launch; nothing is allocated or
+ * copied, so it can be captured into a HIP graph.
+ * FAVIT_ERR_INVALID: a NULL pointer, x == y, g_in or g_out < 1, n_prefix outside {0, 1}, D < 4 or D % 4 != 0;
+ * FAVIT_ERR_UNSUPPORTED: n_prefix + g^2 > FAVIT_POS_RESAMPLE_MAX_L on either side; FAVIT_ERR_ALIGN: x or y not
+ * 16-byte aligned.  Nothing is launched or written then. */
+#define FAVIT_POS_RESAMPLE_MAX_L 16384        /* token rows on either side of favit_pos_resample */
+int favit_pos_resample(const float* x, float* y, const int32_t* rowptr, const int32_t* cols, const float* vals,
+                       int32_t g_in, int32_t g_out, int32_t n_prefix, int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,7 +38,7 @@ def parse_args(argv=None):
     ap.add_argument("--data_dir", default=None, help="dataset directory (--dataset cifar10 or imagenet)")
     ap.add_argument("--subset_size", type=int, default=None)
     ap.add_argument("--num_workers", type=int, default=4)
-    ap.add_argument("--weights", default=None, help="flat state-dict .npz archive (default: the seeded initialisation)")
+    ap.add_argument("--weights", default=None, help="a checkpoint as run_experiment.py's --weights takes (default: the seeded initialisation)")
     ap.add_argument("--dataset", default="cifar10", choices=["cifar10", "imagenet", "default"], help="transform stack")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--img_size", type=int, default=224)

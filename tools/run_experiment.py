@@ -74,46 +74,40 @@ def build_model(pkg, a, classes):
     return model.set_drop_path_rate(rate)
 
 
-def load_flat_weights(model, weights):
-    """Copy a flat state-dict .npz archive (opened without pickle) into the model: a key the archive lacks stays as
-    initialised, a key with another shape is an error.  Returns the names of the keys that were loaded."""
-    loaded = []
-    sd = model.state_dict()
-    with np.load(weights, allow_pickle=False) as arc:
-        for k in arc.files:
-            if k not in sd:
-                continue
-            v = torch.from_numpy(arc[k])
-            if tuple(v.shape) != tuple(sd[k].shape):
-                raise ValueError(f"{weights}: {k} has shape {tuple(v.shape)}, the model's is {tuple(sd[k].shape)}")
-            with torch.no_grad():
-                sd[k].copy_(v)
-            loaded.append(k)
-    return loaded
+def load_flat_weights(model, weights, antialias=True, what="weights"):
+    """Load a checkpoint the user already has into the model through pretrained.load_pretrained and print its report:
+    this project's own flat state-dict .npz (opened without pickle; a key the archive lacks stays as initialised, a key
+    with another shape is an error, as ever), or a torchvision / timm / Hugging Face ViT checkpoint (.pt, .pth, .bin,
+    .npz, .safetensors, an HF directory), whose pos_embed is resampled on the GPU when its grid is not the model's.
+    Returns the names of the keys that were loaded."""
+    pretrained = importlib.import_module("focused-attention-vit_amd").pretrained
+    report = pretrained.load_pretrained(model, weights, pos_embed="resample", antialias=antialias)
+    print(f"{what} {weights}: {report.summary()}")
+    return report["loaded"]
 
 
 def build_teacher(pkg, a, classes):
     """--teacher_experiment: a frozen model of the student's dimensions with dropout 0 and no drop path, in eval mode,
-    with --teacher_weights loaded (the flat .npz --weights takes; for mhla_pretrained the same archive serves both:
+    with --teacher_weights loaded (any checkpoint --weights takes; for mhla_pretrained the same archive serves both:
     the dense model the student's weights came from supervises it).  On the host, like build_model."""
     ta = argparse.Namespace(**vars(a))
     ta.experiment, ta.dropout, ta.drop_path = a.teacher_experiment, 0.0, 0.0
     teacher = build_model(pkg, ta, classes)
-    loaded = load_flat_weights(teacher, a.teacher_weights) if a.teacher_weights else []
+    loaded = (load_flat_weights(teacher, a.teacher_weights, not a.no_pos_antialias, "teacher weights")
+              if a.teacher_weights else [])
     for p in teacher.parameters():
         p.requires_grad = False
     print(f"teacher: {a.teacher_experiment}, {len(loaded)} tensors loaded from {a.teacher_weights}")
     return teacher.eval()
 
 
-def prepare_pretrained(model, weights=None, freeze_layers=False):
+def prepare_pretrained(model, weights=None, freeze_layers=False, antialias=True):
     """The set-up of the reference's two pre-trained experiments (experiments/mhla_pretrained.py:224-247,
-    experiments/sppp_mhla_pretrained.py:236-259).  weights: a flat state-dict .npz archive (opened without pickle);
-    a key the archive lacks stays as initialised, a key with another shape is an error.  Every latent_proj becomes the
+    experiments/sppp_mhla_pretrained.py:236-259).  weights: whatever load_flat_weights takes.  Every latent_proj becomes the
     identity (eye weight, zero bias).  freeze_layers: every parameter whose name contains none of head / latent_proj /
     segmentation / patch_mapper / pooling stops training (the last three only occur in the SPPP models, so this is
     both experiments' rule).  Returns the names of the keys that were loaded."""
-    loaded = load_flat_weights(model, weights) if weights else []
+    loaded = load_flat_weights(model, weights, antialias) if weights else []
     with torch.no_grad():
         for n, mod in model.named_modules():
             if n.endswith("latent_proj") and isinstance(mod, torch.nn.Linear):
@@ -154,7 +148,16 @@ def parse_args(argv=None):
     ap.add_argument("--subset_size", type=int, default=None, help="--data_dir: seeded random subset (test side: a fifth)")
     ap.add_argument("--num_workers", type=int, default=4, help="--data_dir: image decoding threads (at most 16)")
     ap.add_argument("--weights", default=None,
-                    help="*_pretrained: flat state-dict .npz archive; keys it lacks stay as initialised")
+                    help="*_pretrained: a checkpoint on this machine: this project's flat state-dict .npz (keys it lacks stay as "
+                         "initialised), or a torchvision / timm / Hugging Face ViT checkpoint (.pt, .pth, .bin, .npz, "
+                         ".safetensors, an HF directory); a pos_embed of another grid is resampled to --img_size")
+    ap.add_argument("--eval_img_size", type=int, default=None, metavar="S",
+                    help="validate and test at S x S while training stays at --img_size: the models resample pos_embed to "
+                         "the input's patch grid (default: --img_size; S must be a multiple of --patch_size; not for the "
+                         "superpixel experiments)")
+    ap.add_argument("--no_pos_antialias", action="store_true",
+                    help="resample pos_embed with torch's plain bicubic instead of the antialiased one (timm's default), "
+                         "at load time and at another input resolution")
     ap.add_argument("--freeze_layers", action="store_true",
                     help="*_pretrained: train only head, latent_proj and the SPPP components")
     ap.add_argument("--dataset", default="cifar10", choices=["cifar10", "imagenet", "default"], help="transform stack")
@@ -230,7 +233,7 @@ def parse_args(argv=None):
                     help="knowledge distillation: a frozen teacher of this kind with the student's dimensions and dropout 0 "
                          "(default: no teacher)")
     ap.add_argument("--teacher_weights", default=None,
-                    help="--teacher_experiment: flat state-dict .npz archive, as --weights takes (mhla_pretrained: the same file)")
+                    help="--teacher_experiment: a checkpoint as --weights takes (mhla_pretrained: the same file)")
     ap.add_argument("--distill_alpha", type=float, default=0.0,
                     help="training loss = (1 - a) * cross-entropy + a * teacher term (default 0: off; needs a teacher)")
     ap.add_argument("--distill_tau", type=float, default=1.0, help="--distill_type soft: the temperature")
@@ -258,6 +261,11 @@ def parse_args(argv=None):
         ap.error("--distill_alpha > 0 needs --teacher_experiment")
     if a.teacher_weights is not None and a.teacher_experiment is None:
         ap.error("--teacher_weights needs --teacher_experiment")
+    if a.eval_img_size is not None:
+        if a.eval_img_size < a.patch_size or a.eval_img_size % a.patch_size:
+            ap.error("--eval_img_size must be a positive multiple of --patch_size")
+        if a.experiment.startswith("sppp_mhla"):
+            ap.error("--eval_img_size: the superpixel models carry no grid pos_embed to resample")
     if not (a.distill_tau > 0 and a.distill_tau != float("inf")):
         ap.error("--distill_tau must be a finite number > 0")
     return a
@@ -297,8 +305,10 @@ def main(argv=None):
     if train_src is None:
         classes = int(max(ytr.max(), yte.max())) + 1
     model = build_model(pkg, a, classes)
+    if a.no_pos_antialias and hasattr(model, "set_pos_antialias"):
+        model.set_pos_antialias(False)
     if pretrained:
-        loaded = prepare_pretrained(model, a.weights, a.freeze_layers)
+        loaded = prepare_pretrained(model, a.weights, a.freeze_layers, not a.no_pos_antialias)
         n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
         print(f"pretrained set-up: {len(loaded)} tensors loaded from {a.weights}; trainable parameters {n_train:,} of "
               f"{sum(p.numel() for p in model.parameters()):,}")
@@ -308,6 +318,8 @@ def main(argv=None):
         teacher = build_teacher(pkg, a, classes).cuda()
         distill = pkg.train.Distill(a.distill_alpha, a.distill_tau, a.distill_type)
     tfs = pkg.data.get_transforms(a.dataset, a.img_size, seed=a.seed)
+    if a.eval_img_size is not None and a.eval_img_size != a.img_size:
+        tfs["test"] = pkg.data.get_transforms(a.dataset, a.eval_img_size, seed=a.seed)["test"]
     group_kw, opt_kw = {}, {}          # (none of the three flags: exactly the groups and the optimizer of before)
     if a.layer_decay is not None:
         group_kw["layer_decay"] = a.layer_decay
