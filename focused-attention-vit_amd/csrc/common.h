@@ -198,6 +198,13 @@ __device__ __forceinline__ float lane_xor32(float v) {
 __device__ __forceinline__ float quad16_max(float v) { v = fmaxf(v, lane_xor16(v)); return fmaxf(v, lane_xor32(v)); }
 __device__ __forceinline__ float quad16_sum(float v) { v += lane_xor16(v); return v + lane_xor32(v); }
 
+// sum over the 32 lanes of an aligned half wave, in the VALU (DPP within rows of 16, v_permlane16_swap across them)
+__device__ __forceinline__ float half_wave_sum(float v) {
+  v = dpp_sum8(v);
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));  // row_ror:8
+  return v + lane_xor16(v);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -133,13 +133,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   if constexpr (Q8) lnq8_end(q8, qmax, lane, wave);
 }
 
-// sum over the 32 lanes of an aligned half wave, in the VALU (DPP within rows of 16, v_permlane16_swap across them)
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v = dpp_sum8(v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));  // row_ror:8
-  return v + lane_xor16(v);
-}
-
 // Forward for D <= 512: TWO rows per wave, 32 lanes per row, NV float4 per lane.  At D = 384 every lane carries three
 // vectors (the one-row-per-wave kernel above leaves half of its second vector idle and has 1.5 KB in flight per wave),
 // and the two reductions cost five VALU exchanges each instead of six ds_bpermute round trips.

@@ -1832,6 +1832,40 @@ class FinalNormOp:
         return [dx], [dg, db]
 
 
+class HeadPoolOp:
+    """The mean-pooled head (timm's global_pool='avg'): the mean over the token rows [first, L) in place of the CLS row.
+    norm_first: norm(x)[:, first:].mean(1), one fused launch pair per direction (kernels.ln_meanpool_fwd / _bwd);
+    otherwise norm(x[:, first:].mean(1)), timm's fc_norm order (kernels.meanpool_fwd / _bwd around the LayerNorm of
+    the B pooled rows).  Reads every row of x, so the encoder in front of it runs all rows (no cls_only cuts)."""
+
+    def __init__(self, norm_first: bool, first: int = 1, eps: float = 1e-5):
+        self.norm_first, self.first, self.eps = bool(norm_first), int(first), float(eps)
+
+    def fwd(self, ins, prm):
+        (x,), (g, b) = ins, prm
+        B, L, D = x.shape
+        x = _as_f32(x).contiguous()
+        if self.norm_first:
+            y, s, mu, rs = K.ln_meanpool_fwd(x, g, b, self.first, self.eps)
+            return y, (x, s, mu, rs, (g, b), L)
+        p = K.meanpool_fwd(x, self.first)
+        y, mu, rs = K.layernorm_fwd(p, D, g, b, B, D, torch.float32, self.eps)
+        return y, (None, p, mu, rs, (g, b), L)
+
+    def bwd(self, saved, dy, needs):
+        x, s, mu, rs, (g, b), L = saved
+        dy = dy.contiguous()
+        if self.norm_first:
+            dx, dg, db = K.ln_meanpool_bwd(dy, x, g, s, mu, rs, self.first, dg_out=_gt(g), db_out=_gt(b))
+        else:
+            B, D = s.shape
+            dp, _, dg, db = K.layernorm_bwd(dy, s, D, g, mu, rs, B, D, dg_out=_gt(g), db_out=_gt(b))
+            dx = K.meanpool_bwd(dp, L, self.first)
+        if dg is None:
+            _ready(g, b)
+        return [dx], [dg, db]
+
+
 class AttnOp:
     """Stand-alone attention module on fp32 [B, L, D] (no LayerNorm, no residual)."""
 

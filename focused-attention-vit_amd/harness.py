@@ -356,7 +356,12 @@ def attention_maps(model, images: torch.Tensor, per_head: bool = False, residual
                      [B, H, L, W] / [B, H, L, L] (rollout then uses their mean over the heads)
       window         per block its W, 0 for a dense block
       grid           fp32 [B, gh, gw], for models with a patch_embed: rollout[:, 1:] on the patch grid; for a superpixel
-                     model every patch gets the value of the token its superpixel became; None for other models."""
+                     model every patch gets the value of the token its superpixel became; None for other models.
+    A model whose head reads the token mean (set_global_pool('avg')) is refused: these maps follow the CLS row."""
+    pool = getattr(getattr(model, "model", model), "global_pool", "token")
+    if pool != "token":
+        raise ValueError(f"attention_maps: the maps and the rollout describe the CLS row, which the {pool!r}-pooled head "
+                         "of this model does not read; set_global_pool('token') gives the CLS head's maps")
     was_training = model.training
     model.eval()
     try:

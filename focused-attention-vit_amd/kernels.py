@@ -454,6 +454,90 @@ def layernorm_bwd(dy, x, ldx, gamma, mean, rstd, rows, D, *, dres=None, dx=None,
     return (dx, dx_lp, None, None) if acc else (dx, dx_lp, dg, db)
 
 
+def _head_pool_args(who, x, first):
+    """(B, L, D, workspace bytes) of a mean-pooled head call on x fp32 [B, L, D]; the library refuses the widths it has
+    no kernel for before anything is allocated or launched."""
+    require_gpu(x)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{who} expects a contiguous fp32 [B, L, D] tensor")
+    B, L, D = x.shape
+    if not 0 <= int(first) < L:
+        raise ValueError(f"{who}: first = {first} leaves no row of {L} to pool")
+    nbytes = _abi.lib().favit_head_pool_workspace(B, L, int(first), D)
+    if nbytes < 0:
+        _abi.check(int(nbytes), who)
+    return B, L, D, nbytes
+
+
+def _head_pool_row(who, name, t, B, D):
+    require_gpu(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, D):
+        raise ValueError(f"{who}: {name} is a contiguous fp32 [B, D] = [{B}, {D}] tensor")
+
+
+def ln_meanpool_fwd(x, gamma, beta, first=1, eps=1e-5):
+    """x fp32 [B, L, D] -> (y, s, mean, rstd): y [B, D] = mean over the rows [first, L) of LayerNorm(x) (gamma, beta),
+    s [B, D] the mean of the normalised rows before the affine map, mean / rstd [B, L - first] (favit_ln_meanpool_fwd)."""
+    B, L, D, nbytes = _head_pool_args("favit_ln_meanpool_fwd", x, first)
+    require_gpu(gamma, beta)
+    dev, n = x.device, L - int(first)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    y = torch.empty((B, D), dtype=torch.float32, device=dev)
+    s = torch.empty((B, D), dtype=torch.float32, device=dev)
+    mean = torch.empty((B, n), dtype=torch.float32, device=dev)
+    rstd = torch.empty((B, n), dtype=torch.float32, device=dev)
+    _abi.check(_abi.lib().favit_ln_meanpool_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(s), _p(mean), _p(rstd), _p(ws), B, L,
+                                                int(first), D, eps, _st()), "favit_ln_meanpool_fwd")
+    return y, s, mean, rstd
+
+
+def ln_meanpool_bwd(dy, x, gamma, s, mean, rstd, first=1, *, dg_out=None, db_out=None, frozen=False):
+    """(dx [B, L, D] with zeros in the rows below first, dgamma, dbeta) of ln_meanpool_fwd.  dg_out / db_out: fp32 [D]
+    gradient buffers the affine gradients are ACCUMULATED into (then None is returned in their place); frozen: gamma
+    and beta take no gradient."""
+    B, L, D, _ = _head_pool_args("favit_ln_meanpool_bwd", x, first)
+    _head_pool_row("favit_ln_meanpool_bwd", "dy", dy, B, D)
+    _head_pool_row("favit_ln_meanpool_bwd", "s", s, B, D)
+    require_gpu(gamma, mean, rstd)
+    dx = torch.empty((B, L, D), dtype=torch.float32, device=x.device)
+    acc = dg_out is not None and db_out is not None
+    if frozen:
+        dg = db = None
+    elif acc:
+        dg, db = dg_out, db_out
+    else:
+        dgb = torch.empty((2, D), dtype=torch.float32, device=x.device)
+        dg, db = dgb[0], dgb[1]
+    _abi.check(_abi.lib().favit_ln_meanpool_bwd(_p(dy), _p(x), _p(gamma), _p(s), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db),
+                                                int(acc), B, L, int(first), D, _st()), "favit_ln_meanpool_bwd")
+    return (dx, None, None) if acc or frozen else (dx, dg, db)
+
+
+def meanpool_fwd(x, first=1):
+    """x fp32 [B, L, D] -> p [B, D], the mean over the rows [first, L) (favit_meanpool_fwd)."""
+    B, L, D, nbytes = _head_pool_args("favit_meanpool_fwd", x, first)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    p = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    _abi.check(_abi.lib().favit_meanpool_fwd(_p(x), _p(p), _p(ws), B, L, int(first), D, _st()), "favit_meanpool_fwd")
+    return p
+
+
+def meanpool_bwd(dp, L, first=1):
+    """dp fp32 [B, D] -> dx [B, L, D]: dp / (L - first) in the rows [first, L), zeros below (favit_meanpool_bwd)."""
+    require_gpu(dp)
+    if dp.dim() != 2 or dp.dtype != torch.float32 or not dp.is_contiguous():
+        raise ValueError("favit_meanpool_bwd expects a contiguous fp32 [B, D] tensor")
+    B, D = dp.shape
+    if not 0 <= int(first) < L:
+        raise ValueError(f"favit_meanpool_bwd: first = {first} leaves no row of {L} to pool")
+    nbytes = _abi.lib().favit_head_pool_workspace(B, L, int(first), D)       # refuses an unsupported D before dx exists
+    if nbytes < 0:
+        _abi.check(int(nbytes), "favit_meanpool_bwd")
+    dx = torch.empty((B, L, D), dtype=torch.float32, device=dp.device)
+    _abi.check(_abi.lib().favit_meanpool_bwd(_p(dp), _p(dx), B, L, int(first), D, _st()), "favit_meanpool_bwd")
+    return dx
+
+
 def reduce_rows_multi(entries):
     """entries: [(part [2, rows, cols] fp32 contiguous, out0 [cols], out1 [cols])] -> out0 += colsum(part[0]),
     out1 += colsum(part[1]) for every entry in ONE launch (at most 32 entries per launch).  Entries whose row counts

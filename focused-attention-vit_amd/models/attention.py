@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F, params
-from .vit import embed_dropout
+from .vit import embed_dropout, set_global_pool
 
 
 class CrossAttention(nn.Module):
@@ -151,6 +151,8 @@ class CrossAttentionViT(nn.Module):
         x = embed_dropout(x, self.pos_drop.p, self.training)
         for block in self.blocks:
             x = block(x, x)
+        if self.global_pool == "avg":
+            return F.run(F.HeadPoolOp(self.pool_norm == "before"), [x], [self.norm.weight, self.norm.bias])
         return F.run(F.FinalNormOp(), [x], [self.norm.weight, self.norm.bias])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -159,6 +161,9 @@ class CrossAttentionViT(nn.Module):
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool
 
 
 class CrossAttentionSPPPViT(nn.Module):
@@ -209,8 +214,14 @@ class CrossAttentionSPPPViT(nn.Module):
         t = sppp_tokens(self, x)
         for block in self.blocks:
             t = block(t, t)
-        t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
+        if self.global_pool == "avg":
+            t = F.run(F.HeadPoolOp(self.pool_norm == "before"), [t], [self.norm.weight, self.norm.bias])
+        else:
+            t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
         return F.run(F.LinearOp(), [t], [self.head.weight, self.head.bias])
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F
-from .vit import PatchEmbedding, embed_dropout, run_encoder, set_drop_path_rate, set_pos_antialias
+from .vit import PatchEmbedding, embed_dropout, run_encoder, set_drop_path_rate, set_global_pool, set_pos_antialias
 from .sppp import (SuperpixelSegmentation, PatchToSuperpixelMapper, SuperpixelPooling, DynamicPositionalEncoding,
                    calculate_superpixel_centroids, sppp_tokens)
 from .mhla import MHLATransformerBlock
@@ -60,6 +60,9 @@ class PretrainedViTWithMHLA(nn.Module):
         tok = self.patch_embed(x)
         x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
+        if self.global_pool == "avg":
+            x = run_encoder(self.blocks, x, None, self.training, cls_only=False)
+            return F.run(F.HeadPoolOp(self.pool_norm == "before"), [x], [self.norm.weight, self.norm.bias])
         # only the CLS row is read below: the blocks compute just the rows it can see (functional.cls_plan)
         x = run_encoder(self.blocks, x, None, self.training,
                         cls_only=not (self.training and self.pos_drop.p > 0))
@@ -73,6 +76,8 @@ class PretrainedViTWithMHLA(nn.Module):
 
     set_drop_path_rate = set_drop_path_rate
     set_pos_antialias = set_pos_antialias
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool
 
 
 class PretrainedSPPPViTWithMHLA(nn.Module):
@@ -115,12 +120,18 @@ class PretrainedSPPPViTWithMHLA(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         t = sppp_tokens(self, x)
-        t = run_encoder(self.blocks, t, None, self.training,
-                        cls_only=not (self.training and self.pos_embed.dropout.p > 0))
-        t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
+        if self.global_pool == "avg":
+            t = run_encoder(self.blocks, t, None, self.training, cls_only=False)
+            t = F.run(F.HeadPoolOp(self.pool_norm == "before"), [t], [self.norm.weight, self.norm.bias])
+        else:
+            t = run_encoder(self.blocks, t, None, self.training,
+                            cls_only=not (self.training and self.pos_embed.dropout.p > 0))
+            t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
         return F.run(F.LinearOp(), [t], [self.head.weight, self.head.bias])
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     set_drop_path_rate = set_drop_path_rate
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

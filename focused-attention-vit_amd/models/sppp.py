@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F, K, params
-from .vit import PatchEmbedding, TransformerBlock as _VitBlock, run_encoder
+from .vit import PatchEmbedding, TransformerBlock as _VitBlock, run_encoder, set_global_pool
 
 
 class _MapState:
@@ -359,8 +359,14 @@ class SPPPViT(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         t = sppp_tokens(self, x)
         t = run_encoder(self.blocks, t, None, self.training)
-        t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
+        if self.global_pool == "avg":
+            t = F.run(F.HeadPoolOp(self.pool_norm == "before"), [t], [self.norm.weight, self.norm.bias])
+        else:
+            t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
         return F.run(F.LinearOp(), [t], [self.head.weight, self.head.bias])
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F
-from .vit import PatchEmbedding, run_encoder, set_drop_path_rate
+from .vit import PatchEmbedding, run_encoder, set_drop_path_rate, set_global_pool
 from .vit_mhla import TransformerBlock          # byte-identical logic in the reference (sppp_mhla.py:21-110)
 from .sppp import (SuperpixelSegmentation, PatchToSuperpixelMapper, SuperpixelPooling, DynamicPositionalEncoding,
                    calculate_superpixel_centroids, sppp_tokens)
@@ -66,10 +66,15 @@ class SPPPViTMHLA(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         t = sppp_tokens(self, x)
         t = run_encoder(self.blocks, t, None, self.training)       # blocks get no mask (sppp_mhla.py:313-314)
-        t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
+        if self.global_pool == "avg":
+            t = F.run(F.HeadPoolOp(self.pool_norm == "before"), [t], [self.norm.weight, self.norm.bias])
+        else:
+            t = F.run(F.FinalNormOp(), [t], [self.norm.weight, self.norm.bias])
         return F.run(F.LinearOp(), [t], [self.head.weight, self.head.bias])
 
     def get_num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 
     set_drop_path_rate = set_drop_path_rate
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

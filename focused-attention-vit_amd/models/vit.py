@@ -133,6 +133,22 @@ def set_pos_antialias(model, antialias: bool = True):
     return model
 
 
+def set_global_pool(model, pool: str = "token", norm: str = "before"):
+    """What the classification head of a model that ends in `norm` + `head` reads: the CLS row ("token", the default and
+    the reference's rule: functional.FinalNormOp) or the mean over the other token rows ("avg", timm's
+    global_pool="avg": functional.HeadPoolOp).  With "avg", `norm` says where the final LayerNorm sits: "before" the
+    mean (the model's `norm` on every token) or "after" it (timm's fc_norm, which checkpoints trained that way carry;
+    pretrained.Report's pool_hint tells).  The mean reads every row, so a windowed MHLA encoder then runs all its rows
+    instead of the few the CLS row can see.  Plain attributes `global_pool` / `pool_norm`, handled like drop_path: no
+    parameter, no buffer, no state_dict key.  Returns the model."""
+    if pool not in ("token", "avg"):
+        raise ValueError(f"global pool must be 'token' or 'avg', got {pool!r}")
+    if norm not in ("before", "after"):
+        raise ValueError(f"pool norm must be 'before' or 'after', got {norm!r}")
+    model.global_pool, model.pool_norm = pool, norm
+    return model
+
+
 def run_encoder(blocks, x, mask, training, cls_only=False):
     """All blocks of a model as ONE autograd node (no per-block fp32<->bf16 gradient casts) -- or, while
     functional.encoder_segments(n) is active (train.GraphedStep with backward segments), as n consecutive nodes cut
@@ -216,6 +232,8 @@ class VisionTransformer(nn.Module):
         x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
         x = run_encoder(self.blocks, x, None, self.training)
+        if self.global_pool == "avg":
+            return F.run(F.HeadPoolOp(self.pool_norm == "before"), [x], [self.norm.weight, self.norm.bias])
         return F.run(F.FinalNormOp(), [x], [self.norm.weight, self.norm.bias])
 
     def forward(self, x):
@@ -227,3 +245,5 @@ class VisionTransformer(nn.Module):
 
     set_drop_path_rate = set_drop_path_rate
     set_pos_antialias = set_pos_antialias
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 from ._backend import F, params
-from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder, set_drop_path_rate, set_pos_antialias
+from .vit import PatchEmbedding, MLP, embed_dropout, run_encoder, set_drop_path_rate, set_global_pool, set_pos_antialias
 from .mhla import MultiHeadLatentAttention
 
 
@@ -91,6 +91,9 @@ class VisionTransformerMHLA(nn.Module):
         tok = self.patch_embed(x)
         x = F.run(F.PrologueOp(True, self.pos_antialias), [tok], [self.cls_token, self.pos_embed])
         x = embed_dropout(x, self.pos_drop.p, self.training)
+        if self.global_pool == "avg":
+            x = run_encoder(self.blocks, x, None, self.training, cls_only=False)
+            return F.run(F.HeadPoolOp(self.pool_norm == "before"), [x], [self.norm.weight, self.norm.bias])
         # only the CLS row is read below: MHLA stacks compute just the rows it can see (functional.cls_plan)
         x = run_encoder(self.blocks, x, None, self.training,
                         cls_only=not (self.training and self.pos_drop.p > 0))
@@ -105,3 +108,5 @@ class VisionTransformerMHLA(nn.Module):
 
     set_drop_path_rate = set_drop_path_rate
     set_pos_antialias = set_pos_antialias
+    global_pool, pool_norm = "token", "before"     # what the head reads (set_global_pool)
+    set_global_pool = set_global_pool

@@ -8,7 +8,9 @@ What the mapping does (convert_state_dict): renames the keys; turns a convolutio
 Linear over (p1 p2 c) that favit_patchify_fwd feeds (w.permute(0, 2, 3, 1).reshape(D, P*P*C)); concatenates separate q, k
 and v in that order; writes the attention under the names the model owns (attn.qkv / attn.proj, or the in_proj_* /
 out_proj.* of an nn.MultiheadAttention container) and the MLP under fc1 / fc2 or the 0 / 3 of an nn.Sequential.
-latent_proj has no source and stays as it is.  A head of another shape is skipped (the reference re-initialises it);
+latent_proj has no source and stays as it is.  timm's avg-pooled checkpoints carry fc_norm.* in place of norm.*: it
+becomes the model's norm, and the report's pool_hint says how such a model pools (nothing here changes the model's
+pooling: models.vit.set_global_pool does).  A head of another shape is skipped (the reference re-initialises it);
 another patch size, width or depth is an error.  A pos_embed on another grid is resampled on the device
 (functional.pos_resample) by load_pretrained, or refused with pos_embed="strict".
 
@@ -58,7 +60,9 @@ class Report(dict):
     'hf5' = Hugging Face as transformers >= 5 holds it in memory), loaded (model keys that received a tensor), skipped
     ({model key: reason}), unused (source keys nothing was made of), missing (model keys without a source), source_grid
     (side of the source pos_embed's grid, or None), model_grid, pos_embed ('copied', 'resampled' or None),
-    layer_norm_eps (the source's, from a config.json, or None)."""
+    layer_norm_eps (the source's, from a config.json, or None), pool_hint (('avg', 'after') when the model's norm was
+    taken from timm's fc_norm, the LayerNorm behind the token mean: the set_global_pool arguments such a checkpoint was
+    trained with; otherwise None)."""
 
     def summary(self) -> str:
         s = (f"{self['layout']} layout: {len(self['loaded'])} tensors loaded, {len(self['skipped'])} skipped, "
@@ -69,6 +73,9 @@ class Report(dict):
             s += f"\n  skipped {k}: {why}"
         if self["missing"]:
             s += "\n  without a source: " + ", ".join(self["missing"][:8]) + (" ..." if len(self["missing"]) > 8 else "")
+        if self.get("pool_hint") is not None:
+            s += ("\n  norm.* comes from the source's fc_norm: it was trained with set_global_pool"
+                  f"{self['pool_hint']!r}; loading leaves the model's pooling as it is")
         if self.get("layer_norm_eps") is not None:
             s += f"\n  the source was trained with LayerNorm eps = {self['layer_norm_eps']:g}; the model computes with 1e-5"
         return s
@@ -214,7 +221,7 @@ def convert_state_dict(src: Dict[str, torch.Tensor], model: torch.nn.Module) -> 
     msd = model.state_dict()
     layout = detect_layout(src.keys(), msd.keys())
     rep = Report(layout=layout, loaded=[], skipped={}, unused=[], missing=[], source_grid=None, model_grid=None,
-                 pos_embed=None, layer_norm_eps=None)
+                 pos_embed=None, layer_norm_eps=None, pool_hint=None)
     conv: Dict[str, torch.Tensor] = {}
     if layout == "native":
         for k, v in src.items():
@@ -224,6 +231,15 @@ def convert_state_dict(src: Dict[str, torch.Tensor], model: torch.nn.Module) -> 
                 rep["unused"].append(k)
     else:
         canon, rep["unused"] = _canonical(src, layout)
+        fc_norm = [k for k in ("fc_norm.weight", "fc_norm.bias") if k in src] if layout == "timm" else []
+        if fc_norm and any(n.startswith("norm.") for n in canon):
+            rep["unused"] = [f"{k} (the source has norm.*, which the model's norm takes)" if k in fc_norm else k
+                             for k in rep["unused"]]
+        elif fc_norm:
+            for k in fc_norm:
+                canon["norm." + k.split(".")[1]] = src[k]
+                rep["unused"].remove(k)
+            rep["pool_hint"] = ("avg", "after")
         rep["unused"] = sorted(rep["unused"])
         depth, names = _target_names(msd)
         src_depth = 1 + max((int(n.split(".")[1]) for n in canon if n.startswith("blocks.")), default=-1)

@@ -933,6 +933,39 @@ int favit_attn_rollout(int32_t n, const float* const* probs, const int32_t* widt
 int favit_pos_resample(const float* x, float* y, const int32_t* rowptr, const int32_t* cols, const float* vals,
                        int32_t g_in, int32_t g_out, int32_t n_prefix, int32_t D, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Mean-pooled classification head (additive in ABI 8; csrc/head_pool.hip): the mean over the
+ * token rows [first, L) of the encoder output, fused with the final LayerNorm in either order.  Everything is fp32;
+ * x and dx are [B, L, D] contiguous; n = L - first (first = 1 leaves the CLS row out, as timm's global_pool='avg').
+ * Norm-first (the model's `norm` on every token, then the mean):
+ *   ln_meanpool_fwd   y[b] = (1/n) sum_{i >= first} LN(x[b,i]) = gamma * s[b] + beta, s[b] = (1/n) sum_i xhat[b,i];
+ *                     writes y [B,D], s [B,D] and mean / rstd [B,n] of the pooled rows.
+ *   ln_meanpool_bwd   dx[b,i] = the LayerNorm input gradient of the upstream row dy[b] / n (from the saved mean / rstd)
+ *                     for i >= first and ZEROS below (every element of dx is written: no memset by the caller);
+ *                     dgamma (+)= sum_b dy[b] * s[b], dbeta (+)= sum_b dy[b] (accumulate = 1 adds; both NULL: skipped).
+ * Pool-first (timm's fc_norm: the mean, then favit_layernorm_fwd / _bwd on the B pooled rows):
+ *   meanpool_fwd      p[b] = (1/n) sum_{i >= first} x[b,i]
+ *   meanpool_bwd      dx[b,i] = dp[b] / n for i >= first and zeros below.
+ * Forward reads x once: a workgroup sums a chunk of one image's rows (the arithmetic per row is favit_layernorm_fwd's)
+ * into ws IN FP64 (the division by n rounds to fp32 once: s and p are the correctly rounded means of their fp32 terms),
+ * which a second small launch folds in chunk order; ws holds favit_head_pool_workspace bytes (a negative
+ * FAVIT_ERR_* for a refused geometry) and need not be initialised.  Backward reads x once (norm-first) or not at all
+ * and writes dx once.  No atomics and no counters: the same inputs give the same bits in every run and graph replay;
+ * nothing is allocated or synchronised.
+ * FAVIT_ERR_INVALID: a NULL pointer, B, L or D < 1, first outside [0, L), only one of dgamma / dbeta;
+ * FAVIT_ERR_UNSUPPORTED: D % 4 != 0 or D > 2048 (favit_layernorm_fwd's widths); FAVIT_ERR_ALIGN: x, dx, dy, dp, ws,
+ * gamma or beta not 16-byte aligned.  Nothing is launched or written then. */
+int64_t favit_head_pool_workspace(int32_t B, int32_t L, int32_t first, int32_t D);
+int favit_ln_meanpool_fwd(const float* x, const float* gamma, const float* beta, float* y, float* s, float* mean,
+                          float* rstd, void* ws, int32_t B, int32_t L, int32_t first, int32_t D, float eps,
+                          void* stream);
+int favit_ln_meanpool_bwd(const float* dy, const float* x, const float* gamma, const float* s, const float* mean,
+                          const float* rstd, float* dx, float* dgamma, float* dbeta, int32_t accumulate, int32_t B,
+                          int32_t L, int32_t first, int32_t D, void* stream);
+int favit_meanpool_fwd(const float* x, float* p, void* ws, int32_t B, int32_t L, int32_t first, int32_t D,
+                       void* stream);
+int favit_meanpool_bwd(const float* dp, float* dx, int32_t B, int32_t L, int32_t first, int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

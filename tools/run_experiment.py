@@ -64,14 +64,16 @@ def build_model(pkg, a, classes):
     kw = dict(img_size=a.img_size, patch_size=a.patch_size, num_classes=classes, embed_dim=a.embed_dim, depth=a.depth,
               num_heads=a.num_heads, dropout=a.dropout)
     rate = getattr(a, "drop_path", 0.0)
+    pool = (getattr(a, "global_pool", "token"), getattr(a, "pool_norm", "before"))
     if a.experiment == "traditional":
-        return M.vit.VisionTransformer(**kw).set_drop_path_rate(rate)
+        return M.vit.VisionTransformer(**kw).set_drop_path_rate(rate).set_global_pool(*pool)
     if a.experiment in ("mhla", "mhla_pretrained"):
-        return M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True, **kw).set_drop_path_rate(rate)
+        return M.vit_mhla.VisionTransformerMHLA(window_size=a.window_size, use_mhla=True,
+                                                **kw).set_drop_path_rate(rate).set_global_pool(*pool)
     model = M.sppp_mhla.SPPPViTMHLA(num_superpixels=a.num_superpixels, pooling_type=a.pooling_type,
                                     window_size=a.window_size, use_mhla=True, **kw)
     model.segmentation.compactness = a.compactness
-    return model.set_drop_path_rate(rate)
+    return model.set_drop_path_rate(rate).set_global_pool(*pool)
 
 
 def load_flat_weights(model, weights, antialias=True, what="weights"):
@@ -83,6 +85,11 @@ def load_flat_weights(model, weights, antialias=True, what="weights"):
     pretrained = importlib.import_module("focused-attention-vit_amd").pretrained
     report = pretrained.load_pretrained(model, weights, pos_embed="resample", antialias=antialias)
     print(f"{what} {weights}: {report.summary()}")
+    has = (getattr(model, "global_pool", "token"), getattr(model, "pool_norm", "before"))
+    hint = report.get("pool_hint")
+    if hint is not None and hint != has:
+        print(f"{what} {weights}: the checkpoint was trained with --global_pool {hint[0]} --pool_norm {hint[1]}, "
+              f"this run uses --global_pool {has[0]} --pool_norm {has[1]}")
     return report["loaded"]
 
 
@@ -173,6 +180,11 @@ def parse_args(argv=None):
     ap.add_argument("--drop_path", type=float, default=0.0, metavar="RATE",
                     help="stochastic depth: the last block drops each residual branch per sample with this probability, "
                          "block i of depth with RATE * i / (depth - 1) (set_drop_path_rate; not fp8)")
+    ap.add_argument("--global_pool", default="token", choices=["token", "avg"],
+                    help="what the head reads: the CLS row, or the mean over the other tokens (set_global_pool; student "
+                         "and teacher alike).  avg reads every row, so the MHLA models run the dense step")
+    ap.add_argument("--pool_norm", default="before", choices=["before", "after"],
+                    help="--global_pool avg: the final LayerNorm before the mean, or after it (timm's fc_norm)")
     ap.add_argument("--num_superpixels", type=int, default=16)
     ap.add_argument("--compactness", type=float, default=0.1)
     ap.add_argument("--pooling_type", default="mean", choices=["mean", "max", "attention"])
