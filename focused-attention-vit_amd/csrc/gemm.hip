@@ -2115,21 +2115,25 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_s64ln_kernel(KParams p, Ln
     const bool live = m < p.M;
     if (!live) m = p.M - 1;                              // rows past M: a valid row, never stored
     const float* xr = q.x + m * q.ldx;
+    // The two reductions add in the order of ln_fwd_half_kernel (csrc/norm_elem.hip: 32 lanes per row, float4 chunks
+    // l + 32 c per lane, sixteen lanes summed before the two halves meet) and divide by D as it does, so that xn, mean
+    // and rstd are bit for bit those of favit_layernorm_fwd: chunk j16 + 16 i belongs to its lane j16 (i even) or
+    // j16 + 16 (i odd).
     float4 v[NI];
-    float s = 0.f;
+    float s[2] = {0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       v[i] = *reinterpret_cast<const float4*>(xr + 4 * (j16 + 16 * i));
-      s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+      s[i & 1] += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mu = dpp_sum16(s) * (1.0f / (float)D);
-    float qq = 0.f;
+    const float mu = (dpp_sum16(s[0]) + dpp_sum16(s[1])) / (float)D;
+    float qq[2] = {0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const float a = v[i].x - mu, b = v[i].y - mu, c = v[i].z - mu, d = v[i].w - mu;
-      qq += (a * a + b * b) + (c * c + d * d);
+      qq[i & 1] += (a * a + b * b) + (c * c + d * d);
     }
-    const float rs = rsqrtf(dpp_sum16(qq) * (1.0f / (float)D) + q.eps);
+    const float rs = rsqrtf((dpp_sum16(qq[0]) + dpp_sum16(qq[1])) / (float)D + q.eps);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int col = 4 * (j16 + 16 * i);
